@@ -2,6 +2,8 @@
 """bench.py -- env-steps/s + learner updates/s of the 4096-env CartPole PPO hot path on N x MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without WORLD_SIZE: re-executes itself under the launcher below)
+    python bench.py --gpus N --steps K --warmup W --full   (the same line plus every side measurement listed below)
+    python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed to DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +16,9 @@ Workload = BASELINE.json configs[3] per GPU (the config the metric is quoted on;
 DQN sibling and is measured in the `extra` block), synthetic data: random-init weights, Philox-seeded
 env states.  Weak scaling: 4096 envs per GPU, env ids / Philox streams disjoint across ranks.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, pre-heats, warms up, times the K steps and prints the contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with the configuration.  With --full the line also carries
+  ms_per_step_no_preheat  the same K steps timed once before the pre-heat (see PROTOCOL in main())
   roofline      the HBM-bound env-step kernel at the operating point where HBM matters (2^24 envs),
                 achieved = 49 algorithmic bytes x envs / mean launch time (HIP events on the launch stream)
                 (uniformly random actions; `without_terminations` = the same launch when no episode ends)
@@ -23,6 +27,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   kernels       mean per-launch time of every kernel class of the timed workload (HIP events)
   roofline_extra  the side kernels / configs of BASELINE.json (see roofline_extras)
   allreduce     (N > 1 only) latency of the gradient exchange and the library's bus bandwidth sweep
+  replicas_bit_identical  (N > 1 only) every rank's parameters after the timed steps are the same bits
+(--no-extras drops the roofline, cpu_baseline, kernel and allreduce legs from a --full run.)
 """
 import argparse
 import ctypes as C
@@ -1125,12 +1131,39 @@ def preflight(torch, rlhip, rank, local_rank, world, pg, backend):
     dist.destroy_process_group()
 
 
+# what a caller of the timed path receives after one PPO iteration: the learner state (parameters, Adam moments, the loss
+# line) and the trajectory the rollout wrote (observations, actions, rewards, terminals, log-probs, values, advantages, returns)
+DUMP_FIELDS = ("params", "adam_m", "adam_v", "losses", "obs", "action", "reward", "terminal", "logp", "value", "adv", "ret")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(np, pol, out_dir):
+    """--dump-outputs DIR: the arrays of DUMP_FIELDS after the last timed step as DIR/<name>.npy (float32; integer and flag
+    arrays converted exactly), ~6 MB in all.  Same arguments -> same inputs (seeded env states and weights), so two builds
+    can be compared array for array."""
+    tr = pol.trajectory
+    src = {"params": pol.params, "adam_m": pol.m, "adam_v": pol.v, "losses": pol.losses, "obs": tr.obs, "action": tr.action_i,
+           "reward": tr.reward, "terminal": tr.terminal, "logp": tr.logp, "value": tr.value, "adv": tr.adv, "ret": tr.ret}
+    arrays = {k: np.ascontiguousarray(src[k].detach().cpu().numpy().astype(np.float32)) for k in DUMP_FIELDS}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs to dump are {total} bytes, more than {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline / breakdown legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (no-pre-heat timing, rooflines, CPU baseline, kernel breakdown, "
+                         "clock probe; at N > 1 the all-reduce report and the replica check); off: only the timed steps")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline / cpu_baseline / breakdown / allreduce legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32)")
     ap.add_argument("--preflight", action="store_true",
                     help="N > 1 plumbing report (< 10 s of GPU work, no timed steps): peer-access matrix, per-peer IPC mapping, the "
                          "peer-to-peer self-test verdict and why, one exchange through the ABI checked on the host; exits 0")
@@ -1214,7 +1247,7 @@ def main():
     # RLHIP_BENCH_EXTRAS_FIRST=0 restores the old order (legs after the timed region) for an A / B.
     extras = {}
     extras_first = os.environ.get("RLHIP_BENCH_EXTRAS_FIRST", "1") == "1"
-    want_extras = rank == 0 and world == 1 and not args.no_extras
+    want_extras = rank == 0 and world == 1 and args.full and not args.no_extras
 
     def run_extras():
         # order: the idle GPU (CPU baseline) first, the HBM-bound kernels next, the learner legs (whole PPO / DQN iterations,
@@ -1256,14 +1289,22 @@ def main():
     #      back-to-back 5 - 50 us launches needs ~45 steps (~18 ms) before it runs at its steady rate (tools/step_preheat.py;
     #      profiles/r04_rollout.md section 3), so `--steps 20 --warmup 5` alone measures the ramp.
     # Nothing else runs between the two; no leg was added, moved or removed in front of them since round 5.
+    # A plain run (no --full) measures form 2 only: it runs the `preheat_steps` untimed, then the same W + K region.
     preheat = int(os.environ.get("RLHIP_BENCH_PREHEAT_STEPS", "60"))
-    elapsed_np = timed(args.warmup, args.steps)
+    elapsed_np, ran = None, 0
+    if args.full or preheat <= 0:
+        elapsed_np = timed(args.warmup, args.steps)
+        ran = args.warmup + args.steps
     if preheat > 0:
-        for _ in range(max(0, preheat - args.warmup - args.steps)):
+        for _ in range(max(0, preheat - ran)):
             step()
         elapsed = timed(args.warmup, args.steps)
     else:
         elapsed = elapsed_np
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        dump_outputs(np, pol, args.dump_outputs)
 
     env_steps = world * N_ENVS * T_ROLLOUT * args.steps
     updates = pol.n_updates_per_call() * args.steps
@@ -1275,8 +1316,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "ms_per_step_no_preheat": round(elapsed_np / args.steps * 1e3, 4),
-        "value_no_preheat": round(world * N_ENVS * T_ROLLOUT * args.steps / elapsed_np, 1),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1298,6 +1337,9 @@ def main():
         "mean_episode_len_last_rollout": round(
             (N_ENVS * T_ROLLOUT) / max(1.0, float(pol.trajectory.terminal.sum())), 2),
     }
+    if args.full:
+        result["ms_per_step_no_preheat"] = round(elapsed_np / args.steps * 1e3, 4)
+        result["value_no_preheat"] = round(world * N_ENVS * T_ROLLOUT * args.steps / elapsed_np, 1)
     if want_extras:
         result["kernels"] = kernel_breakdown(torch, rlhip, pol, env)
         # (under rocprofv3 -- ROCPROF_* variables / its tool library in LD_PRELOAD -- the leg is skipped: its ~25 000 back-to-back launches would be
@@ -1318,7 +1360,7 @@ def main():
         result["legs_order"] = (f"cpu_baseline, HBM rooflines, learner rooflines, [warmup, timed steps] -> ms_per_step_no_preheat, pre-heat up to {preheat} "
                                 f"untimed steps in total, [warmup, timed steps] -> ms_per_step, kernel breakdown, sustained clock probe"
                                 if extras_first else "[warmup, timed steps], kernel breakdown, cpu_baseline, rooflines")
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         try:  # collective on every rank; a local failure must not cost the bench line
             result["allreduce"] = allreduce_report(torch, pol, world)
         except Exception as exc:  # noqa: BLE001
@@ -1326,7 +1368,7 @@ def main():
     if getattr(pol, "_hipcomm", None) is not None:
         # must be false: a peer that never arrived poisons the step with NaN (csrc/comm.hip) -- also visible in final_loss
         result["p2p_timeouts"] = bool(pol._hipcomm.failed())
-    if world > 1:
+    if world > 1 and args.full:
         # the sharded learner's invariant, checked on the parameters the timed steps produced: every replica applied the
         # same reduced gradient in the same order, so the parameter vectors are bit-identical (MIN / MAX all-reduce of a
         # checksum; outside the timed region)

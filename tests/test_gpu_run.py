@@ -388,13 +388,45 @@ def test_bench_eight_ranks_on_one_device_prints_the_contract_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 8 and d["steps"] == 3 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["n_envs_per_gpu"] == 4096 and d["replicas_bit_identical"] is True
     assert d["p2p_timeouts"] is False and d["gradient_allreduce"].startswith("p2p"), d["gradient_allreduce"]
     assert np.isfinite(d["final_loss"])
+
+
+def test_bench_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """a plain `bench.py --gpus 1` (no --full): the contract fields and no side legs; --dump-outputs writes the last timed
+    step's arrays as float32 .npy files, and a second run with the same arguments writes the same bits"""
+    import json
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(d_out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["metric"] == "env_steps_per_sec" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == 7 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 4096 * 32 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        assert not {"roofline", "roofline_extra", "cpu_baseline", "kernels", "ms_per_step_no_preheat"} & set(d)
+        arrays = {f.name: np.load(f) for f in sorted(d_out.glob("*.npy"))}
+        assert set(arrays) == {"params.npy", "adam_m.npy", "adam_v.npy", "losses.npy", "obs.npy", "action.npy", "reward.npy",
+                               "terminal.npy", "logp.npy", "value.npy", "adv.npy", "ret.npy"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["obs.npy"].shape == (33, 4, 4096) and arrays["params.npy"].size == 3331
+        dumps.append(arrays)
+    for k, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][k]), k
 
 
 @pytest.mark.parametrize("layers,prioritized", [(2, False), (3, False), (2, True)])
@@ -503,7 +535,7 @@ def test_bench_two_ranks_on_one_device_prints_the_contract_line(form):
     env = dict(os.environ, RLHIP_BENCH_SINGLE_DEVICE="1", RLHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")  # RCCL refuses two ranks on one device
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"]
     if form == "bare":
         cmd = [sys.executable] + tail
     else:

@@ -9,9 +9,9 @@ if [ "$1" != "nosuite" ]; then
 ( time timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -14 ) > $O/tests.log 2>&1; cat $O/tests.log
 cp gpurun_out/grad_err.jsonl gpurun_out/bench_shape_margins.jsonl $O/ 2>/dev/null
 fi
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
-bash tools/prof.sh final 2>&1 | tail -10
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench_driver_form.json 2> $O/bench_driver_form.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+bash tools/prof.sh final --full 2>&1 | tail -10
 mkdir -p $O/prof && cp gpurun_out/prof_final.log $O/ && find gpurun_out/prof_final -name "*kernel_stats.csv" -exec cp {} $O/prof/bench_kernel_stats.csv \; && find gpurun_out/prof_final -name "*kernel_trace.csv" -exec cp {} $O/prof/bench_kernel_trace.csv \;
 bash tools/pmc_all.sh > $O/pmc.log 2>&1; tail -40 $O/pmc.log
 cp -r gpurun_out/pmc_all/env.txt gpurun_out/pmc_all/side.txt $O/ 2>/dev/null

@@ -1,5 +1,5 @@
-"""profiles/rNN_final_bench_stats.md (+ rNN_bench_line.json) from a rocprofv3 --kernel-trace --stats run of the default
-bench command (tools/prof.sh final ...):
+"""profiles/rNN_final_bench_stats.md (+ rNN_bench_line.json) from a rocprofv3 --kernel-trace --stats run of the --full
+bench command (tools/prof.sh final --full ...):
     python tools/make_final_profile.py gpurun_out/prof_final gpurun_out/prof_final.log [round = 2] [unprofiled bench json]"""
 import csv, json, os, sys
 
@@ -11,9 +11,9 @@ bench = json.loads(line)
 stats = list(csv.DictReader(open(os.path.join(d, "bench_kernel_stats.csv"))))
 trace = list(csv.DictReader(open(os.path.join(d, "bench_kernel_trace.csv"))))
 out = []
-out.append(f"# Round {rnd} — final state: rocprofv3 `--kernel-trace --stats` of the DEFAULT bench command\n")
+out.append(f"# Round {rnd} — final state: rocprofv3 `--kernel-trace --stats` of the `--full` bench command\n")
 out.append("Command (MI355X box): `rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_final -o bench -- "
-           "python bench.py` (`tools/prof.sh final`; default flags `--gpus 1 --steps 200 --warmup 20`, all legs: timed PPO "
+           "python bench.py --full` (`tools/prof.sh final --full`; default flags `--gpus 1 --steps 200 --warmup 20`, all legs: timed PPO "
            "workload, kernel breakdown, env-step roofline at 2^24 envs, roofline extras incl. the DQN / MFMA / replay "
            "configs, CPU baseline).\n")
 out.append("Bench line printed by the same (profiled) run -- the profiler intercepts every launch, so `ms_per_step` / `value` of a "
