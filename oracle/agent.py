@@ -90,9 +90,9 @@ class DQNRun:
         # optimise!(agent, PostActStage)
         self.vec_steps += 1
         updated = False
+        if self.n_step > 1 and len(self.ring) < self.n_step:  # not one full window yet: the controller is not asked
+            return False
         if len(self.ring) * self.n >= self.min_replay_history and self.vec_steps % self.update_freq == 0 and self._controller_allows():
-            if self.n_step > 1 and len(self.ring) < self.n_step:
-                return False
             gamma = self.gamma
             if self.n_step > 1:
                 idx = B.ring_sample_indices_nstep(self.ring, self.batch, self.n_step, self.sampler_seed, self.draw_ctr)

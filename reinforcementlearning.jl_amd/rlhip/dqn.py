@@ -286,15 +286,17 @@ class DQNLearner:
 
     def optimise_(self, trajectory):
         traces = trajectory.container
+        prioritized = hasattr(traces, "sample_prioritized")
+        if self._nstep is not None and not prioritized and len(traces) < self.n_step:
+            # not one full window yet: the vec-step counts, the controller is not asked (no sample is drawn)
+            self.vec_steps += 1
+            return False
         if not self.should_update_(trajectory):
             return False
         net = self.approximator.network
-        prioritized = hasattr(traces, "sample_prioritized")
         if self._nstep is not None:
             if prioritized:
                 raise NotImplementedError("n-step targets: uniform replay only")
-            if len(traces) < self.n_step:  # not one full window yet
-                return False
             folded, iota = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
             if net.layers == 3:
                 dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, self.approximator.target,
@@ -304,10 +306,7 @@ class DQNLearner:
                 call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params),
                      ptr(self.approximator.target), self.batchsize, ptr(iota), self._nstep.gamma_n, self.delta, ptr(self.workspace),
                      ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
-            self.draw_ctr += 1
-            self.approximator.optimise_(self.grad, clip_norm=self.max_grad_norm, grad_scale=1.0)
-            self.n_updates += 1
-            return True
+            return self._exchange_and_apply_()
         beta = 0.0
         if prioritized:
             beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
@@ -346,6 +345,11 @@ class DQNLearner:
         else:
             dqn_grad(traces, net.hidden, net.n_out, net.act, net.params, self.approximator.target, self.batchsize,
                      self.gamma, self.delta, self.seed, self.draw_ctr, self.workspace, self.grad, self.loss)
+        return self._exchange_and_apply_()
+
+    def _exchange_and_apply_(self):
+        """the tail of every update form (1-step, n-step, prioritized): draw counter, gradient all-reduce over the process group,
+        clip (1 / world scale) + Adam"""
         self.draw_ctr += 1
         scale = 1.0
         if self.process_group is not None:

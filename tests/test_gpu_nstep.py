@@ -171,3 +171,75 @@ def test_per_stage_agent_loop_with_nstep_learner_vs_oracle():
     assert np.quantile(d, 0.99) < 0.2e-3 and d.max() < K * 2e-3 and np.median(np.abs(o.params - p0)) > 1e-3
     with pytest.raises(NotImplementedError):
         rl.run_fused_dqn(agent, env, rl.StopAfterNSteps(1))
+
+
+def _nstep_dqn_agent(rl, n, h, batch, env_seed, explorer_seed, process_group=None):
+    env = rl.CartPoleEnv(n, seed=env_seed)
+    net = rl.HipApproximator(4, h, 2, seed=3)  # the same initial weights on every rank
+    tn = rl.TargetNetwork(net, sync_freq=5)
+    learner = rl.DQNLearner(tn, batchsize=batch, min_replay_history=n, seed=3, n_step=3, process_group=process_group)
+    explorer = rl.EpsilonGreedyExplorer(0.1, kind="exp", decay_steps=10, seed=explorer_seed)
+    traces = rl.CircularArraySARTSTraces(capacity=16, n_env=n, obs_dim=4)
+    return env, rl.Agent(rl.QBasedPolicy(learner, explorer), rl.Trajectory(traces))
+
+
+def _nstep_dqn_worker(rank, world, port, q, K):
+    import os
+    import sys
+
+    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for p in (root, os.path.join(root, "reinforcementlearning.jl_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import torch
+    import torch.distributed as dist
+
+    import rlhip as rl
+
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo")
+    env, agent = _nstep_dqn_agent(rl, 64, 64, 128, env_seed=20 + rank, explorer_seed=30 + rank, process_group=dist.group.WORLD)
+    rl.run(agent, env, rl.StopAfterNSteps(K))
+    torch.cuda.synchronize()
+    learner = agent.policy.learner
+    q.put((rank, learner.approximator.network.params.cpu().numpy(), learner.n_updates))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_nstep_dqn_two_ranks_one_gpu_keep_replicas_identical():
+    """DQNLearner(n_step = 3, process_group) on two ranks with different environments: the n-step update takes the same gradient
+    all-reduce (and 1 / world scale) as the 1-step one, so the replicas stay bit-identical (they drifted apart silently when the
+    n-step branch returned before the exchange)"""
+    import torch.multiprocessing as mp
+
+    from test_gpu_run import _free_port
+
+    world, port, K = 2, _free_port(), 12
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_nstep_dqn_worker, args=(r, world, port, q, K)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=300) for _ in range(world)], key=lambda x: x[0])
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    (_, p0, u0), (_, p1, u1) = res
+    assert u0 == u1 == K - 2
+    assert np.array_equal(p0, p1)
+
+
+def test_nstep_window_filling_does_not_count_a_sample():
+    """while the trajectory holds fewer than n_step transitions no update happens, and the sample / insert controller is not
+    asked (it used to count a sample for each of those vec-steps); the vec-step counter still advances once per call"""
+    import rlhip as rl
+
+    for K, sampled in ((2, 0), (3, 1)):
+        env, agent = _nstep_dqn_agent(rl, 16, 32, 16, env_seed=1, explorer_seed=1)
+        rl.run(agent, env, rl.StopAfterNSteps(K))
+        torch.cuda.synchronize()
+        learner = agent.policy.learner
+        assert learner.vec_steps == K and learner.n_updates == sampled
+        assert agent.trajectory.controller.n_sampled == sampled
