@@ -610,6 +610,10 @@ static int32_t rollout_entry(int32_t kind, const void* env_cfg, const rlhip_env_
                              const rlhip_ppo_cfg* cfg, const float* params, uint64_t seed, uint32_t env_id_base,
                              uint32_t vec_step0, const uint32_t* ctr, const rlhip_ppo_traj* traj,
                              rlhip_stream_t stream) {
+    // the policy head has env_na(kind) = 3 actions for a discrete Pendulum (make_desc): an env of another action count would
+    // map the sampled index onto its own torque grid and never see its last actions
+    RLHIP_REQUIRE(kind != 1 || !cfg || cfg->continuous || !env_cfg || ((const rlhip_pendulum_cfg*)env_cfg)->n_actions == 3,
+                  "PPO on a discrete Pendulum needs n_actions = 3 (the policy head has 3 actions)");
     if (is_layers3(cfg)) {
         RLHIP_REQUIRE(ctr == nullptr, "layers = 3: the device-counter (graph replay) variant is not built");
         return ppo3_rollout(kind, env_cfg, st, n, T, cfg, params, seed, env_id_base, vec_step0, traj, stream);

@@ -83,6 +83,11 @@ class PPOPolicy:
         nparams_fn, init_fn = ("rlhip_mlp2_nparams", "rlhip_mlp2_init_f32") if self.layers == 2 else \
             ("rlhip_mlp3_nparams", "rlhip_mlp3_init_f32")
         self.np_actor = int(getattr(_lib.lib, nparams_fn)(ns, self.cfg.hidden, nout_a))
+        if self.np_actor + int(getattr(_lib.lib, nparams_fn)(ns, self.cfg.hidden, 1)) != self.np:
+            # the kernels size the actor head by the env kind (2 actions for CartPole, 3 for Pendulum and MountainCar):
+            # a discrete env with another action count has no policy here (and the critic's init would write past params)
+            raise _lib.RLHipArgumentError(f"PPOPolicy: {self.na} actions, but the policy head of this env has a fixed "
+                                          "action count (a discrete PendulumEnv needs n_actions = 3)")
         if params is None:
             self.params = torch.empty(self.np, dtype=torch.float32, device=dev)
             # glorot_uniform(rng) stand-in: actor net_id 0, critic net_id 1 (Philox INIT stream)
