@@ -15,11 +15,10 @@
 //                     H1 tile in LDS -> MFMA -> H2 in registers -> head through a wave-private LDS transposition of the
 //                     wave's own 64 x 32 block -> loss line per sample on wave 0 (modes: PPO actor, PPO critic, DQN target
 //                     network = forward only, DQN online network) -> dZ2 in the MFMA D layout; db2 / dW3 / db3 and the loss
-//                     sums stay in registers across tiles.  dZ2 leaves as bf16 ONCE since round 6, in MFMA fragment order (the
-//                     D registers as they are: 512 B contiguous per store instruction, no transposition), one buffer per net, kept
-//                     until the dW2 launch.  (Rounds 2 - 5 wrote a row-major image for the backward kernel as well -- half of
-//                     the kernel's store bytes: the tile's stores are a serialised ~2000-cycle resource of the CU, and one image
-//                     less took 7 us off each forward launch; RLHIP_W3_DZ_ONCE above.)
+//                     sums stay in registers across tiles.  dZ2 leaves as bf16 in ONE image, in MFMA fragment order (the D
+//                     registers as they are: 512 B contiguous per store instruction, no transposition), one buffer per net, read
+//                     by the backward kernel and kept until the dW2 launch.  (The row-major forms measured against it, rows only
+//                     and both images: profiles/r06_ppo3w.md sections 3 - 5.)
 //   ppo3w_bwd_kernel  W2^T fragments resident.  dZ2 fragment tile -> LDS, copied lane-linear (double-buffered, register-staged two
 //                     passes ahead); the A operand (lane = sample row) is read out of it TRANSPOSED: two ds_read_b64_tr_b16 per
 //                     fragment -> MFMA -> dH1 in registers; z1 is recomputed from the observation (ns <= 4 FMAs per element:
@@ -74,28 +73,16 @@ __host__ __device__ __forceinline__ int mlp3w_ns_small(int ns, int nout) { retur
 // per-phase cycle stamps of one steady-state tile (workgroup 0, thread 0, its second / third tile): -DRLHIP_W3_TIMING.
 // PROPORTIONS ONLY: the stamps change the register allocation (the backward kernel spilled 584 bytes per lane in one timing
 // build and ran 4x slower than the shipped one) -- kernel times come from rocprofv3 on the normal build.
-// RLHIP_W3_DZ_ONCE (round 6, VERDICT r5 item 2 "dZ2 written once"): the forward kernel writes dZ2 in ONE layout (rounds 2 - 5: two, rows
-// for the backward kernel and MFMA B-fragment order for the dW2 kernel; -128 MB written and -128 MB read per optimiser step of a PPO pair,
-// half of the forward kernel's store bytes -- and the tile's stores are what that kernel's passes wait for).  Which one:
-//   2 (shipped)  the FRAGMENT image: the forward kernel's D registers leave as they are (no transposition through the wave's private LDS
-//                block), the dW2 kernel loads its B operand as in rounds 2 - 5, and the BACKWARD kernel -- whose A operand is the transposed
-//                view, lane = sample row -- copies the tile lane-linear into LDS and reads it with ds_read_b64_tr_b16 (two per fragment)
-//   1            the ROW image: forward transposes, backward reads rows as in rounds 2 - 5, the dW2 kernel stages the rows in LDS and
-//                gathers its fragments with the transposing reads (first form of the round; 9 - 12 us per optimiser step slower than 2)
-//   0            both images (rounds 2 - 5), kept for A / B
-// RLHIP_W3_DZF_PAD (mode 2): four 16-byte slots of padding behind every 32 of the backward kernel's LDS copy make the transposing reads
+// The dZ2 hand-over: the forward kernel's D registers leave as they are, as the FRAGMENT image (no transposition through the wave's
+// private LDS block); the dW2 kernel loads it as its B operand, and the BACKWARD kernel -- whose A operand is the transposed view, lane =
+// sample row -- copies the tile lane-linear into LDS and reads it with ds_read_b64_tr_b16 (two per fragment).
+// RLHIP_W3_DZF_PAD: four 16-byte slots of padding behind every 32 of the backward kernel's LDS copy make the transposing reads
 // bank-conflict free: the kernel -3 us per launch (30.5 -> 27.5), 5 % fewer cycles per optimiser step.  On boxes without an active clock limiter
 // that is -9 us per step (188.5 -> 179.3); on the others the firmware then runs the whole step at a LOWER clock (2.11 - 2.21 vs 2.29 - 2.35 GHz at
 // 1.05 vs 1.16 kW under a 1.4 kW cap) and the step is 2 - 3 % SLOWER.  Both kernels are always built; the macro / the environment variable of
 // the same name select 0 = unpadded, 1 = padded, 2 ("auto", the default) = by the chip's clock (W3Pad below); profiles/r06_ppo3w.md section 5.
-#ifndef RLHIP_W3_DZ_ONCE
-#define RLHIP_W3_DZ_ONCE 2
-#endif
 #ifndef RLHIP_W3_DZF_PAD
 #define RLHIP_W3_DZF_PAD 2
-#endif
-#ifndef RLHIP_W3_FWD_T
-#define RLHIP_W3_FWD_T 1  // the forward-only modes of ppo3w_fwd_kernel compute layer 2 transposed: the head in-lane, no LDS transposition (0: as the others)
 #endif
 #ifndef RLHIP_W3_TIMING_NET
 #define RLHIP_W3_TIMING_NET 0  // which mode of ppo3w_fwd_kernel a -DRLHIP_W3_TIMING build stamps (0 PPO actor ... 2 DQN target network, forward only)
@@ -159,7 +146,6 @@ struct P3WArgs {
     const float* rec;        // [n T][8] {x0..x3, old log-prob, advantage, return, action}: ppo3w_update's record copy, or NULL
     float* xg;               // [NS][npad] the micro-batch's observations in sample order (ppo3w_gather_kernel), npad = ntiles RW
     float* sg;               // [4][npad]  old log-prob | advantage (0 on padding) | return | action (float or int bits)
-    uint16_t* dz_rows;       // [ntiles * RW][HW] bf16
     uint16_t* dz_frag;       // [nets][ntiles][RW / 16][WV][64 lanes][8] bf16 (PPO: one buffer per net, frag_stride apart)
     int64_t frag_stride;     // elements between the nets' fragment buffers (0: one net)
     float* partS;            // [rows][npS]: partial gradients of the small tensors, [actor small | critic small]
@@ -362,7 +348,6 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 // ------------------------------------------------------------------------------------------------ forward + loss + dZ2
 constexpr int TPW = 36;  // f32 pitch of a wave's private 64 x 32 transposition block (144 B rows)
-[[maybe_unused]] constexpr int ZPW = 40;  // bf16 pitch of the same block when it holds the wave's dZ2 columns (80 B rows)
 constexpr size_t FWDW_LDS = (MAXO * RW + WV * MAXO * RW + SMALLWW + WV * RW * TPW) * sizeof(float) +
                             (size_t)RW * PW * sizeof(uint16_t);
 
@@ -384,11 +369,8 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_fwd_kernel(P3WArgs g) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, kb = lane >> 5;
     const int col = 32 * w + r;
-    constexpr bool FWD_T = RLHIP_W3_FWD_T && (NET == 2 || NET == 4);  // forward-only modes compute layer 2 transposed (see the MFMA loop)
+    constexpr bool FWD_T = NET == 2 || NET == 4;  // forward-only modes compute layer 2 transposed (see the MFMA loop)
     float* l_tw = l_t + w * RW * TPW;
-#if RLHIP_W3_DZ_ONCE != 2
-    uint16_t* l_zw = reinterpret_cast<uint16_t*>(l_tw);  // the wave's dZ2 columns as bf16 rows (the row image's copy-out)
-#endif
     const float* pnet = NET == 2 ? g.tparams : g.params + ((NET == 1 || NET == 4) ? g.np_a : 0);
     const float* xsrc = NET == 2 ? g.xg2 : g.xg;
     // every global load of the prologue is issued before the first wait: fragments, tile 0's inputs, the small tensors
@@ -711,8 +693,7 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_fwd_kernel(P3WArgs g) {
         }  // forward only: the other waves are already in the next pass's layer 1
         __syncthreads();  // D: dL/d(head outputs) of the tile
         W3_STAMP(0, 5);
-        // ---- head backward in the MFMA D layout: dW3, dh2 -> dz2 (f32) -> db2; dz2 -> bf16: fragments straight to global,
-        //      rows through the wave's private block (64 rows x 64 B of this wave's columns, no workgroup barrier) ----
+        // ---- head backward in the MFMA D layout: dW3, dh2 -> dz2 (f32) -> db2; dz2 -> bf16 fragments straight to global ----
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
@@ -731,13 +712,9 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_fwd_kernel(P3WArgs g) {
                 const float dz = dh * act_bwd_t<ACT>(hv, hv);  // relu: h2 > 0 <=> z2 > 0
                 a_db2 += dz;
                 h2[rt][q] = dz;  // the register is free: keep dz for the packed stores below
-#if RLHIP_W3_DZ_ONCE != 2
-                l_zw[row * ZPW + r] = f32_to_bf16_rne(dz);
-#endif
             }
             // fragment order: samples 32 rt + 8 gq + 4 kb + {0..3} of column `col` = bytes 8 kb .. 8 kb + 7 of slot
             // (k-step 2 rt + (gq >> 1), column tile w, lane 32 (gq & 1) + r)
-#if RLHIP_W3_DZ_ONCE != 1
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 uint2 v2;
@@ -746,21 +723,8 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_fwd_kernel(P3WArgs g) {
                 const int64_t slot = (((int64_t)tile * (RW / 16) + 2 * rt + (gq >> 1)) * WV + w) * 64 + 32 * (gq & 1) + r;
                 *reinterpret_cast<uint2*>(g.dz_frag + (NET == 1 ? g.frag_stride : 0) + slot * 8 + 4 * kb) = v2;
             }
-#endif
         }
         W3_STAMP(0, 6);
-#if RLHIP_W3_DZ_ONCE != 2
-        wave_lds_fence();
-        {
-            uint16_t* dst = g.dz_rows + (int64_t)tile * RW * HW + 32 * w;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = lane + 64 * i, row = c >> 2, cc = c & 3;
-                *reinterpret_cast<uint4*>(dst + row * HW + 8 * cc) = *reinterpret_cast<const uint4*>(l_zw + row * ZPW + 8 * cc);
-            }
-        }
-        wave_lds_fence();
-#endif
         W3_STAMP(0, 7);
         // no barrier: the next pass writes l_H (last read before barrier C) and this wave's private block in program order
     }
@@ -801,34 +765,12 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_fwd_kernel(P3WArgs g) {
 // PAD (template parameter of the backward kernel, chosen per launch: w3_dzf_pad()): the padded LDS copy of the fragment tile, see RLHIP_W3_DZF_PAD
 template <bool PAD>
 struct Dzf {
-#if RLHIP_W3_DZ_ONCE == 2
     static constexpr int G = PAD ? 72 : 64, H = PAD ? 36 : 32;  // 16-byte slots per 64-slot group / per 32-slot half of the LDS copy
     static constexpr int TILE = (RW / 16) * WV * G * 8;         // elements of one copy (32 KB; 36 KB padded)
-#else
-    static constexpr int TILE = RW * PW;
-#endif
     static constexpr size_t LDS = (2 * WV * 4 * RW + HW * 4 + HW) * sizeof(float) + (size_t)2 * TILE * sizeof(uint16_t);
 };
 
-// this thread's four 16-byte chunks of a 64 x 256 bf16 tile: chunk c = tid + 512 i -> row c >> 5, column 8 (c & 31)
-__device__ __forceinline__ void load_dz_tile(const uint16_t* __restrict__ dz_rows, int tile, int tid, nt_u32x4 (&d)[4]) {
-    const uint16_t* src = dz_rows + (int64_t)tile * RW * HW;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = tid + NTW * i, row = c >> 5, cc = c & 31;
-        d[i] = *reinterpret_cast<const nt_u32x4*>(src + row * HW + 8 * cc);
-    }
-}
-__device__ __forceinline__ void store_dz_tile(uint16_t* lH, int tid, const nt_u32x4 (&d)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = tid + NTW * i, row = c >> 5, cc = c & 31;
-        *reinterpret_cast<nt_u32x4*>(lH + row * PW + 8 * cc) = d[i];
-    }
-}
-
-#if RLHIP_W3_DZ_ONCE == 2
-// RLHIP_W3_DZ_ONCE == 2: the ONE image of dZ2 is the fragment image [tile][k-step s >> 4][column tile j >> 5][slot 32 ((s >> 3) & 1) +
+// The ONE image of dZ2 is the fragment image [tile][k-step s >> 4][column tile j >> 5][slot 32 ((s >> 3) & 1) +
 // (j & 31)][u = s & 7] (what the forward kernel's D registers store without any transposition, and what the dW2 kernel loads as its B
 // operand).  This kernel needs the transposed view -- A operand of dH1 = dZ2 W2: lane = sample row, 8 consecutive columns j -- and takes
 // it from a lane-linear LDS copy of the tile with two transposing reads per fragment: in 16-lane group G (rows 16 (G & 1) + 0 .. 15 of
@@ -866,12 +808,6 @@ __device__ __forceinline__ bf16x8 dzf_a_frag(const uint16_t* lF, int base, int r
     const nt_u32x4 u = {l2.x, l2.y, h2.x, h2.y};
     return __builtin_bit_cast(bf16x8, u);
 }
-#define W3_LOAD_DZ(tile_, d_) load_dzf_tile(g.dz_frag + (net ? g.frag_stride : 0), tile_, tid, d_)
-#define W3_STORE_DZ(l_, d_) store_dzf_tile<PAD>(l_, tid, d_)
-#else
-#define W3_LOAD_DZ(tile_, d_) load_dz_tile(g.dz_rows, tile_, tid, d_)
-#define W3_STORE_DZ(l_, d_) store_dz_tile(l_, tid, d_)
-#endif
 
 template <int NS, int ACT, bool PAD>
 __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
@@ -879,7 +815,7 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
     extern __shared__ __attribute__((aligned(16))) char smw[];
     float* l_x = reinterpret_cast<float*>(smw);  // [2][WV][4][RW]: every wave keeps its own copy of the tile's observations
     float* l_w = l_x + 2 * WV * 4 * RW;          // W1 | b1
-    uint16_t* l_H = reinterpret_cast<uint16_t*>(l_w + HW * 4 + HW);  // [2][RW][PW] dZ2 rows, double-buffered
+    uint16_t* l_H = reinterpret_cast<uint16_t*>(l_w + HW * 4 + HW);  // [2][BWD_TILE_ELEMS] LDS copies of the dZ2 fragment tile, double-buffered
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, kb = lane >> 5;
@@ -903,20 +839,20 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
         float x0[NS];
         // issue order = the steady state of the pass loop (older: everything the prologue itself consumes; then set 0, then
         // set 1), so that the loop is entered with exactly the outstanding loads its back edge carries
-        W3_LOAD_DZ(t0, d0);
+        load_dzf_tile(g.dz_frag + (net ? g.frag_stride : 0), t0, tid, d0);
         load_x<NS>(g, t0, lane, x0);
         constexpr int NWL = (HW * NS + HW + NTW - 1) / NTW;
         float wv[NWL];
 #pragma unroll
         for (int i = 0; i < NWL; ++i) wv[i] = (tid + NTW * i < HW * NS + HW) ? pnet[tid + NTW * i] : 0.0f;
-        W3_LOAD_DZ(min(t0 + stride, last), dzs[0]);
+        load_dzf_tile(g.dz_frag + (net ? g.frag_stride : 0), min(t0 + stride, last), tid, dzs[0]);
         load_x<NS>(g, min(t0 + stride, last), lane, xr[0]);
-        W3_LOAD_DZ(min(t0 + 2 * stride, last), dzs[1]);
+        load_dzf_tile(g.dz_frag + (net ? g.frag_stride : 0), min(t0 + 2 * stride, last), tid, dzs[1]);
         load_x<NS>(g, min(t0 + 2 * stride, last), lane, xr[1]);
 #pragma unroll
         for (int i = 0; i < NWL; ++i)
             if (tid + NTW * i < HW * NS + HW) l_w[tid + NTW * i] = wv[i];
-        W3_STORE_DZ(l_H, d0);
+        store_dzf_tile<PAD>(l_H, tid, d0);
         store_x<NS>(l_xw, lane, x0);
     }
     __syncthreads();
@@ -939,9 +875,9 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
         {
             int t3 = tile + 3 * stride;  // past the end: re-read this workgroup's OWN first tile (never one tile for all)
             if (t3 > last) t3 = blockIdx.x;
-            W3_STORE_DZ(l_H + (p ^ 1) * BWD_TILE_ELEMS, dzs[p]);
+            store_dzf_tile<PAD>(l_H + (p ^ 1) * BWD_TILE_ELEMS, tid, dzs[p]);
             store_x<NS>(l_xw + (p ^ 1) * WV * 4 * RW, lane, xr[p]);
-            W3_LOAD_DZ(t3, dzs[p]);
+            load_dzf_tile(g.dz_frag + (net ? g.frag_stride : 0), t3, tid, dzs[p]);
             load_x<NS>(g, t3, lane, xr[p]);
         }
         W3_STAMP(1, 1);
@@ -951,27 +887,16 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) dh[rt][q] = 0.0f;
         {
-#if RLHIP_W3_DZ_ONCE == 2
             const int abase = dzf_lane_base<PAD>(lane);
 #pragma unroll
             for (int ks = 0; ks < KSW; ++ks) {
-                if ((ks & 3) == 0 && ks) __builtin_amdgcn_sched_barrier(0);  // (as in the dW2 kernel: bounds how far the LDS reads are hoisted)
+                if ((ks & 3) == 0 && ks) __builtin_amdgcn_sched_barrier(0);  // bounds how far the LDS reads are hoisted
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
                     const bf16x8 a = dzf_a_frag<PAD>(lH, abase, rt, ks);
                     dh[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bw[ks], dh[rt], 0, 0, 0);
                 }
             }
-#else
-            const uint16_t* ap = lH + r * PW + 8 * kb;
-#pragma unroll
-            for (int ks = 0; ks < KSW; ++ks)
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
-                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + 32 * rt * PW + 16 * ks);
-                    dh[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bw[ks], dh[rt], 0, 0, 0);
-                }
-#endif
         }
         W3_STAMP(1, 2);
         // z1 = b1 + W1 x of the tile in the layout of dH1 (lane = hidden unit, registers = sample rows) on the f32 MFMA:
@@ -1050,36 +975,13 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_bwd_kernel(P3WArgs g, int net) {
 }
 
 // ------------------------------------------------------------------------------------------------ dW2 = H1^T dZ2
-constexpr size_t DW2W_LDS = (2 * WV * 4 * RW + HW * 4 + HW) * sizeof(float) + (size_t)2 * (HW / 2) * PT * sizeof(uint16_t)
-#if RLHIP_W3_DZ_ONCE == 1
-                            + (size_t)2 * RW * PW * sizeof(uint16_t)  // the tile's dZ2 ROWS, double-buffered (as ppo3w_bwd_kernel stages them)
-#endif
-    ;
+constexpr size_t DW2W_LDS = (2 * WV * 4 * RW + HW * 4 + HW) * sizeof(float) + (size_t)2 * (HW / 2) * PT * sizeof(uint16_t);
 
 __device__ __forceinline__ void load_dz_frags(const uint16_t* __restrict__ dz_frag, int tile, int w, int lane,
                                               bf16x8 (&b)[RW / 16]) {
 #pragma unroll
     for (int ks = 0; ks < RW / 16; ++ks)
         b[ks] = *reinterpret_cast<const bf16x8*>(dz_frag + ((((int64_t)tile * (RW / 16) + ks) * WV + w) * 64 + lane) * 8);
-}
-
-// RLHIP_W3_DZ_ONCE: the same fragments out of the ROW image dz[tile * RW + sample][HW].  The tile's rows travel global -> registers
-// (16-byte coalesced loads two passes ahead: load_dz_tile) -> LDS [RW][PW] in front of the pass's one barrier (store_dz_tile), and a
-// lane gathers the fragment of k-step ks -- samples 16 ks + 8 kb + 0 .. 7 of column 32 w + r -- out of it.
-// (First form tried: eight 2-byte reads per fragment straight from global memory, no LDS: ppo3w_dw2_kernel 43.8 -> 57.4 us; tools/contacts_r06/r6_m.sh.)
-// Two transposing LDS reads per fragment (ds_read_b64_tr_b16; semantics pinned by tools/micro/tr16_probe.hip: within a 16-lane group,
-// lane g passes the address of M[R0 + (g >> 2)][C0 + 4 (g & 3)] and receives M[R0 .. R0 + 3][C0 + g]): group G = lane >> 4 covers columns
-// 32 w + 16 (G & 1) + 0 .. 15 of the k half kb = G >> 1, rows 16 ks + 8 kb + {0 .. 3 | 4 .. 7}.
-// (Second form tried: eight 2-byte LDS reads + four packs per fragment: 42.1 -> 53.0 us.)
-__device__ __forceinline__ bf16x8 gather_dz_col(const uint16_t* lD, int ks, int w, int lane) {
-    const int G = lane >> 4, g = lane & 15;
-    const uint16_t* src = lD + (16 * ks + 8 * (G >> 1) + (g >> 2)) * PW + 32 * w + 16 * (G & 1) + 4 * (g & 3);
-    typedef __attribute__((address_space(3))) tr_v4s* lds_v4s_ptr;
-    const tr_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(src));
-    const tr_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(src + 4 * PW));
-    const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);  // (whole registers: no 16-bit shuffling)
-    const nt_u32x4 u = {l2.x, l2.y, h2.x, h2.y};
-    return __builtin_bit_cast(bf16x8, u);
 }
 
 template <int NS, int ACT>
@@ -1120,12 +1022,7 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_dw2_kernel(P3WArgs g, int net_ar
     // the tile of pass it + 2 right after its MFMAs (two passes in flight); the gather alternates between waves 7 and 6
     // observations: set it & 1 holds tile + 1 at the top of pass `it`, lands in the other LDS copy, is re-issued with tile + 3
     // (indices clamped to the last tile instead of branching: unconditional loads keep the vmcnt bookkeeping exact)
-#if RLHIP_W3_DZ_ONCE == 1
-    nt_u32x4 dzs[2][4];  // this thread's four 16-byte chunks of a tile's rows, two tiles in flight
-    uint16_t* l_dz = l_T + 2 * (HW / 2) * PT;  // [2][RW][PW]
-#else
     bf16x8 bq[2][RW / 16];
-#endif
     float xr[2][NS];
     const int last = g.ntiles - 1;
     {
@@ -1138,15 +1035,9 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_dw2_kernel(P3WArgs g, int net_ar
 #pragma unroll
         for (int i = 0; i < NWL; ++i) wv[i] = (tid + NTW * i < HW * NS + HW) ? pnet[tid + NTW * i] : 0.0f;
         load_x<NS>(g, min(sr + nsr, last), lane, xr[0]);
-#if RLHIP_W3_DZ_ONCE == 1
-        load_dz_tile(dzf, min(sr, last), tid, dzs[0]);
-        load_x<NS>(g, min(sr + 2 * nsr, last), lane, xr[1]);
-        load_dz_tile(dzf, min(sr + nsr, last), tid, dzs[1]);
-#else
         load_dz_frags(dzf, min(sr, last), w, lane, bq[0]);
         load_x<NS>(g, min(sr + 2 * nsr, last), lane, xr[1]);
         load_dz_frags(dzf, min(sr + nsr, last), w, lane, bq[1]);
-#endif
 #pragma unroll
         for (int i = 0; i < NWL; ++i)
             if (tid + NTW * i < HW * NS + HW) l_w[tid + NTW * i] = wv[i];
@@ -1176,11 +1067,6 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_dw2_kernel(P3WArgs g, int net_ar
         uint16_t* lT = l_T + p * (HW / 2) * PT;
         store_x<NS>(l_xw + (p ^ 1) * WV * 4 * RW, lane, xr[p]);
         load_x<NS>(g, min(tile + 3 * nsr, last), lane, xr[p]);
-#if RLHIP_W3_DZ_ONCE == 1
-        uint16_t* lD = l_dz + p * RW * PW;
-        store_dz_tile(lD, tid, dzs[p]);  // this pass's rows (requested two passes ago); read behind the pass's barrier
-        load_dz_tile(dzf, min(tile + 2 * nsr, last), tid, dzs[p]);
-#endif
         wave_lds_fence();
         W3_STAMP(2, 1);
         // ---- layer 1 in [k][sample] order for the 128 hidden units of this half, on the f32 MFMA (bit-identical to the
@@ -1206,32 +1092,15 @@ __global__ __launch_bounds__(NTW, 2) void ppo3w_dw2_kernel(P3WArgs g, int net_ar
         }
         __syncthreads();  // the one barrier of a pass
         W3_STAMP(2, 2);
-#if RLHIP_W3_DZ_ONCE == 1
-        bf16x8 bnx = gather_dz_col(lD, 0, w, lane);
-#endif
 #pragma unroll
-        for (int ks = 0; ks < RW / 16; ++ks) {
-#if RLHIP_W3_DZ_ONCE == 1
-            // the fragment of k-step ks + 1 is requested in front of the MFMAs of k-step ks; the scheduling barrier keeps the scheduler from
-            // hoisting all 24 LDS reads of a pass to its top (256 registers + spills without it)
-            const bf16x8 bfr = bnx;
-            if (ks + 1 < RW / 16) bnx = gather_dz_col(lD, ks + 1, w, lane);
-            if (ks == 2) __builtin_amdgcn_sched_barrier(0);
-#endif
+        for (int ks = 0; ks < RW / 16; ++ks)
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(lT + (32 * kt + r) * PT + 16 * ks + 8 * kb);
-#if RLHIP_W3_DZ_ONCE == 1
-                acc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfr, acc[kt], 0, 0, 0);
-#else
                 acc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[p][ks], acc[kt], 0, 0, 0);
-#endif
             }
-        }
         W3_STAMP(2, 3);
-#if RLHIP_W3_DZ_ONCE != 1
         load_dz_frags(dzf, min(tile + 2 * nsr, last), w, lane, bq[p]);
-#endif
         W3_STAMP(2, 4);
     };
     const int npass = (g.ntiles - sr + nsr - 1) / nsr;
@@ -1714,13 +1583,8 @@ constexpr int P3W_ROWS_S = 512;  // upper bound of the persistent workgroups (= 
 constexpr int P3W_ROWS_W = 128;  // sample ranges (= partial rows) of the dW2 kernel; its grid is twice that (two k halves)
 constexpr int64_t P3W_MAX_TILES = 1 << 20;
 
-template <typename K>
-static int32_t allow_lds_w(K kernel, size_t bytes, unsigned long long* done) { return allow_big_lds(kernel, bytes, done); }
-
-static int p3w_rows_w() { return P3W_ROWS_W; }
-
 struct P3WLayout {
-    int64_t ntiles, off_xg, off_sg, off_rows, off_frag, off_partS, off_partW, off_loss, off_tail, off_rec, bytes;
+    int64_t ntiles, off_xg, off_sg, off_frag, off_partS, off_partW, off_loss, off_tail, off_rec, bytes;
     int npS, nS_a;
 };
 
@@ -1735,8 +1599,6 @@ static P3WLayout p3w_layout(int ns, int nout_a, const rlhip_ppo_cfg* c, int64_t 
     o += 4 * L.ntiles * RW * (int64_t)sizeof(float);
     L.off_sg = o;
     o += 4 * L.ntiles * RW * (int64_t)sizeof(float);
-    L.off_rows = o;
-    o += L.ntiles * RW * HW * (int64_t)sizeof(uint16_t);
     L.off_frag = o;
     o += 2 * L.ntiles * RW * HW * (int64_t)sizeof(uint16_t);  // one fragment buffer per net (the dW2 launch reads both)
     L.off_partS = o;
@@ -1823,7 +1685,6 @@ static void w3pad_init(W3Pad& P) {
 }
 // one call per backward launch
 static bool w3_dzf_pad() {
-    if (RLHIP_W3_DZ_ONCE != 2) return false;
     std::lock_guard<std::mutex> lk(g_w3pad_mu);
     W3Pad& P = g_w3pad;
     if (P.mode < 0) w3pad_init(P);
@@ -1873,22 +1734,19 @@ extern "C" int32_t rlhip_debug_w3_dzf_pad_info(int32_t on, double* info) {
     if (info != nullptr) {
         info[0] = P.mode, info[1] = P.variant, info[2] = P.last_mhz, info[3] = P.top_mhz, info[4] = P.switches, info[5] = P.path[0] != 0;
     }
-    return RLHIP_W3_DZ_ONCE == 2 ? P.variant : 0;
+    return P.variant;
 }
 extern "C" int32_t rlhip_debug_w3_dzf_pad(int32_t on) {
     const int32_t prev = rlhip_debug_w3_dzf_pad_info(-1, nullptr);
     if (on >= 0) rlhip_debug_w3_dzf_pad_info(on, nullptr);
     return prev;
 }
+// the backward kernel with the LDS copy w3_dzf_pad() picks (the caller raises the LDS limit of both before its first launch)
 #define W3_LAUNCH_BWD(NS_, ACT_, net_)                                                                                               \
     do {                                                                                                                             \
-        static unsigned long long dp0_ = 0, dp1_ = 0;                                                                                \
-        int32_t rcb_;                                                                                                                \
         if (w3_dzf_pad()) {                                                                                                          \
-            if ((rcb_ = allow_lds_w(ppo3w_bwd_kernel<NS_, ACT_, true>, Dzf<true>::LDS, &dp1_))) return rcb_;                         \
             hipLaunchKernelGGL((ppo3w_bwd_kernel<NS_, ACT_, true>), dim3(nrowsS), dim3(NTW), Dzf<true>::LDS, s, g, net_);            \
         } else {                                                                                                                     \
-            if ((rcb_ = allow_lds_w(ppo3w_bwd_kernel<NS_, ACT_, false>, Dzf<false>::LDS, &dp0_))) return rcb_;                       \
             hipLaunchKernelGGL((ppo3w_bwd_kernel<NS_, ACT_, false>), dim3(nrowsS), dim3(NTW), Dzf<false>::LDS, s, g, net_);          \
         }                                                                                                                            \
     } while (0)
@@ -1945,9 +1803,9 @@ static int32_t rollout3w_impl(const typename P::cfg_t* cfg, const rlhip_env_stat
 #define LAUNCH_RW(ACT_)                                                                                            \
     do {                                                                                                           \
         static unsigned long long done_ = 0, donev_ = 0;                                                           \
-        int32_t rc_ = allow_lds_w(ppo3w_rollout_kernel<P, 2, ACT_, false>, ROLLW_LDS, &done_);                     \
+        int32_t rc_ = allow_big_lds(ppo3w_rollout_kernel<P, 2, ACT_, false>, ROLLW_LDS, &done_);                   \
         if (rc_) return rc_;                                                                                       \
-        if ((rc_ = allow_lds_w(ppo3w_fwd_kernel<NS, 1, ACT_, 0, 4>, FWDW_LDS, &donev_))) return rc_;               \
+        if ((rc_ = allow_big_lds(ppo3w_fwd_kernel<NS, 1, ACT_, 0, 4>, FWDW_LDS, &donev_))) return rc_;             \
         hipLaunchKernelGGL((ppo3w_rollout_kernel<P, 2, ACT_, false>), grid, dim3(NTW), ROLLW_LDS, s, p, a, n, (int)T, pd.cont, \
                            pd.na, params, pd.np_a, seed, env_id_base, vec_step0, tr, pd.gamma, pd.lambda);         \
         hipLaunchKernelGGL((ppo3w_fwd_kernel<NS, 1, ACT_, 0, 4>), dim3(nwg), dim3(NTW), FWDW_LDS, s, g);           \
@@ -2031,7 +1889,6 @@ static int32_t ppo3w_grad_impl(int32_t kind, const rlhip_ppo_cfg* cfg, const Pol
     g.gamma = 0.0f;
     g.delta = 0.0f;
     g.rec = (tail != nullptr && tail->rec_ready) ? (const float*)(ws + L.off_rec) : nullptr;
-    g.dz_rows = (uint16_t*)(ws + L.off_rows);
     g.dz_frag = (uint16_t*)(ws + L.off_frag);
     g.frag_stride = L.ntiles * RW * HW;
     g.partS = (float*)(ws + L.off_partS);
@@ -2074,19 +1931,19 @@ static int32_t ppo3w_grad_impl(int32_t kind, const rlhip_ppo_cfg* cfg, const Pol
         }
     }
     // the dW2 launch covers both nets (blockIdx.y): 2 k halves x nsr sample ranges x 2 nets = one workgroup per CU at nsr = 64
-    const int rows_w = (p3w_rows_w() + 1) / 2;
+    const int rows_w = (P3W_ROWS_W + 1) / 2;
     const int nsr = (int)(L.ntiles < rows_w ? L.ntiles : rows_w);
 #define LAUNCH_GW(NS_, ACT_, CONT_)                                                                                   \
     do {                                                                                                              \
-        static unsigned long long d0_ = 0, d1_ = 0, d3_ = 0;                                                       \
+        static unsigned long long d0_ = 0, d1_ = 0, d3_ = 0, dp1_ = 0, dp0_ = 0;                                      \
         int32_t rc_;                                                                                                  \
-        if ((rc_ = allow_lds_w(ppo3w_fwd_kernel<NS_, 2, ACT_, CONT_, 0>, FWDW_LDS, &d0_))) return rc_;                \
-        if ((rc_ = allow_lds_w(ppo3w_fwd_kernel<NS_, 1, ACT_, CONT_, 1>, FWDW_LDS, &d1_))) return rc_;                \
-        if ((rc_ = allow_lds_w(ppo3w_dw2_kernel<NS_, ACT_>, DW2W_LDS, &d3_))) return rc_;                             \
-        if (RLHIP_W3_DZ_ONCE == 1) g.dz_rows = g.dz_frag; /* one row image per net, kept for the dW2 launch */              \
+        if ((rc_ = allow_big_lds(ppo3w_fwd_kernel<NS_, 2, ACT_, CONT_, 0>, FWDW_LDS, &d0_))) return rc_;              \
+        if ((rc_ = allow_big_lds(ppo3w_fwd_kernel<NS_, 1, ACT_, CONT_, 1>, FWDW_LDS, &d1_))) return rc_;              \
+        if ((rc_ = allow_big_lds(ppo3w_dw2_kernel<NS_, ACT_>, DW2W_LDS, &d3_))) return rc_;                           \
+        if ((rc_ = allow_big_lds(ppo3w_bwd_kernel<NS_, ACT_, true>, Dzf<true>::LDS, &dp1_))) return rc_;              \
+        if ((rc_ = allow_big_lds(ppo3w_bwd_kernel<NS_, ACT_, false>, Dzf<false>::LDS, &dp0_))) return rc_;            \
         hipLaunchKernelGGL((ppo3w_fwd_kernel<NS_, 2, ACT_, CONT_, 0>), dim3(nrowsS), dim3(NTW), FWDW_LDS, s, g);      \
         W3_LAUNCH_BWD(NS_, ACT_, 0);                                                                                  \
-        if (RLHIP_W3_DZ_ONCE == 1) g.dz_rows = g.dz_frag + g.frag_stride;                                                  \
         hipLaunchKernelGGL((ppo3w_fwd_kernel<NS_, 1, ACT_, CONT_, 1>), dim3(nrowsS), dim3(NTW), FWDW_LDS, s, g);      \
         W3_LAUNCH_BWD(NS_, ACT_, 1);                                                                                  \
         hipLaunchKernelGGL((ppo3w_dw2_kernel<NS_, ACT_>), dim3(2 * nsr, 2), dim3(NTW), DW2W_LDS, s, g, -1, nsr);      \
@@ -2341,7 +2198,7 @@ __global__ __launch_bounds__(NTW) void dqn3w_plan_kernel(const float* __restrict
 }
 
 struct D3WLayout {
-    int64_t ntiles, npad, off_xg, off_xg2, off_sg, off_rows, off_frag, off_partS, off_partW, off_loss, off_tail, bytes;
+    int64_t ntiles, npad, off_xg, off_xg2, off_sg, off_frag, off_partS, off_partW, off_loss, off_tail, bytes;
     int nS;
 };
 
@@ -2358,8 +2215,6 @@ static D3WLayout d3w_layout(int ns, int na, int64_t batch) {
     o += 4 * L.npad * (int64_t)sizeof(float);
     L.off_sg = o;
     o += 4 * L.npad * (int64_t)sizeof(float);
-    L.off_rows = o;
-    o += L.npad * HW * (int64_t)sizeof(uint16_t);
     L.off_frag = o;
     o += L.npad * HW * (int64_t)sizeof(uint16_t);
     L.off_partS = o;
@@ -2392,7 +2247,7 @@ int32_t dqn3w_plan(const float* params, const uint16_t* packed, int64_t ns, int6
 #define LAUNCH_PW(NS_, NA_, ACT_)                                                                                       \
     do {                                                                                                                \
         static unsigned long long done_ = 0;                                                                                      \
-        int32_t rc_ = allow_lds_w(dqn3w_plan_kernel<NS_, NA_, ACT_>, PLANW_LDS, &done_);                                \
+        int32_t rc_ = allow_big_lds(dqn3w_plan_kernel<NS_, NA_, ACT_>, PLANW_LDS, &done_);                              \
         if (rc_) return rc_;                                                                                            \
         hipLaunchKernelGGL((dqn3w_plan_kernel<NS_, NA_, ACT_>), grid, dim3(NTW), PLANW_LDS, s, params, packed, obs, n, eps, \
                            seed, env_id_base, step, actions, q_out);                                                    \
@@ -2435,7 +2290,6 @@ int32_t dqn3w_grad(const rlhip_ring* rb, int64_t na, int32_t act, const float* p
     g.xg = (float*)(ws + L.off_xg);
     g.xg2 = (float*)(ws + L.off_xg2);
     g.sg = (float*)(ws + L.off_sg);
-    g.dz_rows = (uint16_t*)(ws + L.off_rows);
     g.dz_frag = (uint16_t*)(ws + L.off_frag);
     g.partS = (float*)(ws + L.off_partS);
     g.partW = (float*)(ws + L.off_partW);
@@ -2458,16 +2312,17 @@ int32_t dqn3w_grad(const rlhip_ring* rb, int64_t na, int32_t act, const float* p
     g.delta = huber_delta;
     const int n_cu = device_cu_count() < P3W_ROWS_S ? device_cu_count() : P3W_ROWS_S;
     const int nrowsS = (int)(L.ntiles < n_cu ? L.ntiles : n_cu);
-    const int nsr = (int)(L.ntiles < p3w_rows_w() ? L.ntiles : p3w_rows_w());
+    const int nsr = (int)(L.ntiles < P3W_ROWS_W ? L.ntiles : P3W_ROWS_W);
     const int gb = (g.npad + 255) / 256;
 #define LAUNCH_DW(NS_, NA_, ACT_)                                                                                      \
     do {                                                                                                               \
-        static unsigned long long d0_ = 0, d1_ = 0, d3_ = 0;                                                        \
+        static unsigned long long d0_ = 0, d1_ = 0, d3_ = 0, dp1_ = 0, dp0_ = 0;                                       \
         int32_t rc_;                                                                                                   \
-        if ((rc_ = allow_lds_w(ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 2>, FWDW_LDS, &d0_))) return rc_;                   \
-        if ((rc_ = allow_lds_w(ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 3>, FWDW_LDS, &d1_))) return rc_;                   \
-        if ((rc_ = allow_lds_w(ppo3w_dw2_kernel<NS_, ACT_>, DW2W_LDS, &d3_))) return rc_;                              \
-        if (RLHIP_W3_DZ_ONCE == 1) g.dz_rows = g.dz_frag; /* the one dZ2 image (rows), read by bwd AND dw2 */                \
+        if ((rc_ = allow_big_lds(ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 2>, FWDW_LDS, &d0_))) return rc_;                 \
+        if ((rc_ = allow_big_lds(ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 3>, FWDW_LDS, &d1_))) return rc_;                 \
+        if ((rc_ = allow_big_lds(ppo3w_dw2_kernel<NS_, ACT_>, DW2W_LDS, &d3_))) return rc_;                            \
+        if ((rc_ = allow_big_lds(ppo3w_bwd_kernel<NS_, ACT_, true>, Dzf<true>::LDS, &dp1_))) return rc_;               \
+        if ((rc_ = allow_big_lds(ppo3w_bwd_kernel<NS_, ACT_, false>, Dzf<false>::LDS, &dp0_))) return rc_;             \
         hipLaunchKernelGGL((dqn3w_gather_kernel<NS_>), dim3(gb), dim3(256), 0, s, r, g);                               \
         hipLaunchKernelGGL((ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 2>), dim3(nrowsS), dim3(NTW), FWDW_LDS, s, g);         \
         hipLaunchKernelGGL((ppo3w_fwd_kernel<NS_, NA_, ACT_, 0, 3>), dim3(nrowsS), dim3(NTW), FWDW_LDS, s, g);         \
