@@ -719,7 +719,10 @@ typedef struct {
     int32_t n_epochs, n_microbatches;
     int32_t hidden, act;
     int32_t continuous;          /* 0 categorical actor; 1 gaussian actor (mu, log sigma) */
-    int32_t normalize_advantage; /* reserved, must be 0 */
+    int32_t normalize_advantage; /* 0 or 1: the removed RLZoo PPO's option, per (epoch, micro-batch) of bm = n T / n_microbatches
+                                  * samples: adv = (float)((adv - mean) / clamp(std, 1e-8, 1000)) with the Float64 mean and the
+                                  * corrected two-pass std (divisor bm - 1, or 1 when bm <= 1); see rlhip_ppo_adv_normalize_f32.
+                                  * Every grad / update entry point honours it (the multi-GPU ones only at world = 1) */
     int32_t layers;              /* 2 (default; 0 means 2): ns -> hidden -> nout on the VALU (ppo.hip / ppo_grad.hip);
                                   * 3: ns -> hidden -> hidden -> nout actor and critic with the hidden x hidden layer on the
                                   * bf16 MFMA, hidden = 128 (ppo3.hip) or 256 (ppo3w.hip), BASELINE configs[2]
@@ -778,6 +781,21 @@ int32_t rlhip_ppo_gae_f32(const rlhip_ppo_cfg* cfg_host, int64_t n, int64_t T,
  * once after allocation (it holds counters and epoch words that the kernels maintain themselves): rlhip_ppo_workspace_init
  * does that and registers its size. */
 int64_t rlhip_ppo_workspace_bytes(int32_t kind, const rlhip_ppo_cfg* cfg_host, int64_t n, int64_t T);
+/* Advantage normalisation (cfg.normalize_advantage = 1) of micro-batch `mb` of epoch `epoch_ctr`: the samples the epoch's keyed
+ * permutation puts at positions [mb bm, (mb + 1) bm), bm = n T / n_microbatches.  adv_out[f] = (float)((adv[f] - mu) / sd) for
+ * those trajectory entries f (all others untouched), stats_out (device, nullable): double[2] = {mu, sd}, the Float64 mean and
+ * the clamped corrected std.  The sums run in a fixed tree (bit-identical from run to run; the oracle sums sequentially).
+ * The gradient / update entry points run the same kernels for every micro-batch of an epoch at once, into a region behind the
+ * flag-off workspace: rlhip_ppo_update*_f32 once per epoch; rlhip_ppo_grad*_f32 on every call (three launches over all n T
+ * entries per micro-batch gradient -- the host-stepped sequences, the world = 1 sharded routes among them, pay that per step).
+ * With the flag on, rlhip_ppo_workspace_bytes = R(W) + R(4 n T) + S, W = the flag-off size, R(x) = 256 ceil(x / 256), and
+ *   S = R(4 n T) + R(8 ceil(n T / 1024) n_mb + 16 n_mb) + 256   for n_mb = n_microbatches <= 64,
+ *   S = R(16 n_mb (ceil(bm / 2048) + 1))                         above
+ * (the normalised plane; per-entry micro-batch indices, Float64 partial sums, statistics and a counter).  The sharded updates (rlhip_ppo_update_p2p_f32,
+ * rlhip_ppo_update_comm_f32) return RLHIP_EINVAL with the flag on and world > 1: per-rank statistics are not those of one GPU
+ * with a world-times larger batch. */
+int32_t rlhip_ppo_adv_normalize_f32(const rlhip_ppo_cfg* cfg_host, int64_t n, int64_t T, const float* adv, uint64_t seed,
+                                    uint32_t epoch_ctr, int32_t mb, float* adv_out, double* stats_out, rlhip_stream_t stream);
 /* ABI 2: REGISTER a workspace before its first use: zero-fills `bytes` bytes on `stream` (the counters and epoch words the
  * kernels maintain) and records (pointer -> bytes) in a host-side table.  Every rlhip_ppo_grad* / rlhip_ppo_apply_f32 /
  * rlhip_ppo_update* call compares rlhip_ppo_workspace_bytes(kind, cfg, n, T) of THAT call with the registered size and returns

@@ -922,10 +922,21 @@ int32_t ppo3_update(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, int64_t T
     bool packed_fresh = false;  // the previous optimiser step's fused tail left the bf16 W2 images up to date
     for (int32_t e = 0; e < cfg->n_epochs; ++e) {
         const uint32_t epoch_ctr = update_ctr * (uint32_t)cfg->n_epochs + (uint32_t)e;
+        const rlhip_ppo_traj* te = traj;
+        rlhip_ppo_traj tn;
+        if (cfg->normalize_advantage) {  // the epoch's normalised plane (ppo_advnorm.hip) in place of traj->adv
+            RLHIP_REQUIRE(traj != nullptr, "NULL argument");
+            float* plane = nullptr;
+            int32_t rcn = advnorm_epoch(kind, cfg, n, T, traj->adv, seed, epoch_ctr, nullptr, workspace, &plane, as_stream(stream));
+            if (rcn) return rcn;
+            tn = *traj;
+            tn.adv = plane;
+            te = &tn;
+        }
         for (int32_t mb = 0; mb < cfg->n_microbatches; ++mb) {
             bool fused = false;
             const P3Tail tail{params, m, v, beta_pow, &fused};
-            int32_t rc = ppo3_grad_impl(kind, cfg, n, T, traj, params, seed, epoch_ctr, mb, workspace, grad_scratch,
+            int32_t rc = ppo3_grad_impl(kind, cfg, n, T, te, params, seed, epoch_ctr, mb, workspace, grad_scratch,
                                         losses_out, /*do_pack=*/!packed_fresh, stream, &tail);
             if (rc) return rc;
             packed_fresh = fused;

@@ -1985,9 +1985,10 @@ int32_t ppo3w_update(int32_t kind, const rlhip_ppo_cfg* cfg, const PolicyDesc& p
     const int ns = kind == 0 ? 4 : 3;
     const int64_t np = ppo3w_nparams(ns, pd.nout_a);
     (void)np;
-    bool rec_ready = false;
-    {
-        RLHIP_REQUIRE(traj->obs && traj->logp && traj->adv && traj->ret && (pd.cont ? (const void*)traj->action_f : (const void*)traj->action_i),
+    // the record copy of the trajectory (advantages from `adv`); with normalize_advantage it is re-built once per epoch
+    // from that epoch's normalised plane
+    auto build_rec = [&](const float* adv) -> int32_t {
+        RLHIP_REQUIRE(traj->obs && traj->logp && adv && traj->ret && (pd.cont ? (const void*)traj->action_f : (const void*)traj->action_i),
                       "trajectory array is NULL");
         const int64_t total = n * T;
         RLHIP_REQUIRE(total >= 1 && total <= 0x7FFFFFFFll, "n * T out of range");
@@ -1995,7 +1996,7 @@ int32_t ppo3w_update(int32_t kind, const rlhip_ppo_cfg* cfg, const PolicyDesc& p
         P3WArgs g{};
         g.obs = traj->obs;
         g.logp = traj->logp;
-        g.adv = traj->adv;
+        g.adv = adv;
         g.ret = traj->ret;
         g.action_f = traj->action_f;
         g.action_i = traj->action_i;
@@ -2006,13 +2007,21 @@ int32_t ppo3w_update(int32_t kind, const rlhip_ppo_cfg* cfg, const PolicyDesc& p
         hipStream_t s = as_stream(stream);
         if (kind == 0) hipLaunchKernelGGL((ppo3w_build_rec_kernel<4, 0>), dim3(gb), dim3(256), 0, s, g, rec);
         else hipLaunchKernelGGL((ppo3w_build_rec_kernel<3, 1>), dim3(gb), dim3(256), 0, s, g, rec);
-        rec_ready = true;
-    }
-    const P3WTail tail{params, m, v, beta_pow, rec_ready};
+        return RLHIP_OK;
+    };
+    if (!cfg->normalize_advantage)
+        if (int32_t rcb = build_rec(traj->adv)) return rcb;
+    const P3WTail tail{params, m, v, beta_pow, true};
     const bool fused = true;
     bool packed_fresh = false;  // the previous optimiser step's tail left the bf16 images of both W2 up to date
     for (int32_t e = 0; e < cfg->n_epochs; ++e) {
         const uint32_t epoch_ctr = update_ctr * (uint32_t)cfg->n_epochs + (uint32_t)e;
+        if (cfg->normalize_advantage) {
+            float* plane = nullptr;
+            int32_t rcn = advnorm_epoch(kind, cfg, n, T, traj->adv, seed, epoch_ctr, nullptr, workspace, &plane, as_stream(stream));
+            if (rcn) return rcn;
+            if ((rcn = build_rec(plane))) return rcn;
+        }
         for (int32_t mb = 0; mb < cfg->n_microbatches; ++mb) {
             int32_t rc = ppo3w_grad_impl(kind, cfg, pd, n, T, traj, params, seed, epoch_ctr, mb, workspace, grad_scratch,
                                          losses_out, /*do_pack=*/!packed_fresh, &tail, stream);

@@ -41,6 +41,12 @@ int32_t ppo3_update(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, int64_t T
                     float* params, float* m, float* v, float* beta_pow, uint64_t seed, uint32_t update_ctr,
                     void* workspace, float* grad_scratch, float* losses_out, rlhip_stream_t stream);
 
+// normalize_advantage = 1 (ppo_advnorm.hip): the region behind the learner's own workspace carve, and the launches that fill
+// its plane with one epoch's normalised advantages (epoch = the epoch counter, or with ctr the epoch inside the update call)
+int64_t advnorm_region_bytes(const rlhip_ppo_cfg* c, int64_t n, int64_t T);
+int32_t advnorm_epoch(int32_t kind, const rlhip_ppo_cfg* c, int64_t n, int64_t T, const float* adv, uint64_t seed,
+                      uint32_t epoch, const uint32_t* ctr, void* workspace, float** plane, hipStream_t s);
+
 static inline int64_t env_na(int kind, int cont) { return cont ? 1 : (kind == 0 ? 2 : 3); }
 
 static inline int32_t make_desc(int32_t kind, const rlhip_ppo_cfg* c, PolicyDesc* pd) {
@@ -48,7 +54,7 @@ static inline int32_t make_desc(int32_t kind, const rlhip_ppo_cfg* c, PolicyDesc
     RLHIP_REQUIRE(c != nullptr, "ppo cfg is NULL");
     RLHIP_REQUIRE(c->hidden >= 4 && c->hidden % 4 == 0, "hidden must be a positive multiple of 4");
     RLHIP_REQUIRE(c->act == 0 || c->act == 1, "act must be 0 (relu) or 1 (tanh)");
-    RLHIP_REQUIRE(c->normalize_advantage == 0, "normalize_advantage is not supported yet");
+    RLHIP_REQUIRE(c->normalize_advantage == 0 || c->normalize_advantage == 1, "normalize_advantage must be 0 or 1");
     RLHIP_REQUIRE(c->layers == 0 || c->layers == 2 || c->layers == 3, "layers must be 2 or 3");
     int ns = kind == 0 ? 4 : (kind == 1 ? 3 : 2);
     pd->h = c->hidden;

@@ -770,10 +770,31 @@ int32_t rlhip_ppo_workspace_release(void* workspace) {
 }
 
 int64_t rlhip_ppo_workspace_bytes(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, int64_t T) {
-    if (is_layers3(cfg)) return ppo3_workspace_bytes(kind, cfg, n, T);
-    int64_t np = rlhip_ppo_nparams(kind, cfg);
-    if (np < 0) return -1;
-    return grad_workspace_bytes(np) + sample_record_bytes(n, T);
+    // normalize_advantage = 1: the normalisation region (ppo_advnorm.hip) goes behind the flag-off size rounded up to 256
+    const bool norm = cfg != nullptr && cfg->normalize_advantage;
+    int64_t b;
+    if (is_layers3(cfg)) {
+        b = ppo3_workspace_bytes(kind, cfg, n, T);
+        if (b < 0) return b;
+    } else {
+        int64_t np = rlhip_ppo_nparams(kind, cfg);
+        if (np < 0) return -1;
+        b = grad_workspace_bytes(np) + sample_record_bytes(n, T);
+    }
+    return norm ? (b + 255) / 256 * 256 + advnorm_region_bytes(cfg, n, T) : b;
+}
+
+// normalize_advantage = 1: one epoch's normalised advantages into the workspace, and `tn` = *traj reading them
+static int32_t normalized_traj(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, int64_t T, const rlhip_ppo_traj* traj,
+                               uint64_t seed, uint32_t epoch, const uint32_t* ctr, void* workspace, rlhip_ppo_traj* tn,
+                               hipStream_t s) {
+    RLHIP_REQUIRE(traj != nullptr, "NULL argument");
+    if (int32_t rc = ws_check(kind, cfg, n, T, workspace)) return rc;
+    float* plane = nullptr;
+    if (int32_t rc = advnorm_epoch(kind, cfg, n, T, traj->adv, seed, epoch, ctr, workspace, &plane, s)) return rc;
+    *tn = *traj;
+    tn->adv = plane;
+    return RLHIP_OK;
 }
 
 
@@ -782,6 +803,15 @@ static int32_t grad_entry(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, int
                           void* workspace, float* grad_out, float* losses_out, rlhip_stream_t stream,
                           bool do_pack = true) {
     RLHIP_REQUIRE(grad_out != nullptr, "grad_out is NULL");
+    rlhip_ppo_traj tn;
+    if (cfg != nullptr && cfg->normalize_advantage) {
+        // the epoch's whole plane, recomputed by every call: the gradient then reads it where it would read traj->adv
+        RLHIP_REQUIRE(!(is_layers3(cfg) && ctr != nullptr), "layers = 3: the device-counter (graph replay) variant is not built");
+        RLHIP_REQUIRE(cfg->n_microbatches >= 1 && mb >= 0 && mb < cfg->n_microbatches, "bad micro-batch index");
+        if (int32_t rcn = normalized_traj(kind, cfg, n, T, traj, seed, epoch_ctr, ctr, workspace, &tn, as_stream(stream)))
+            return rcn;
+        traj = &tn;
+    }
     if (is_layers3(cfg)) {
         RLHIP_REQUIRE(ctr == nullptr, "layers = 3: the device-counter (graph replay) variant is not built");
         if (int32_t rcw = ws_check(kind, cfg, n, T, workspace)) return rcw;
@@ -853,6 +883,8 @@ int32_t rlhip_ppo_update_p2p_f32(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t
                                  float* losses_out, int32_t rank, int32_t world, void* const* comm_bufs_host,
                                  int64_t comm_cap, uint32_t seq0, int64_t timeout_polls, int32_t* status_dev,
                                  rlhip_stream_t stream) {
+    // per-rank statistics would not be those of the single GPU with a world-times larger batch
+    RLHIP_REQUIRE(!(cfg && cfg->normalize_advantage && world > 1), "normalize_advantage is not supported with world > 1");
     RLHIP_REQUIRE(cfg && params && m && v && beta_pow && grad_scratch && comm_bufs_host && status_dev, "NULL argument");
     RLHIP_REQUIRE(world >= 1, "bad world size");
     const int64_t np = rlhip_ppo_nparams(kind, cfg);
@@ -871,7 +903,8 @@ int32_t rlhip_ppo_update_p2p_f32(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t
     }
     const int rblocks = (int)((np + RP - 1) / RP);
     float4* samples = is_layers3(cfg) ? nullptr : update_samples_ptr(kind, cfg, n, T, workspace);
-    const bool fused = !is_layers3(cfg) && rblocks <= grid_apply_max_blocks<APPLY_XCHG>() && world <= 16 &&
+    // (normalize_advantage, world = 1: the step-by-step route, whose gradient calls normalise)
+    const bool fused = !is_layers3(cfg) && !cfg->normalize_advantage && rblocks <= grid_apply_max_blocks<APPLY_XCHG>() && world <= 16 &&
                        comm_cap <= (1 << 24) && !RLHIP_ENV_FLAG("RLHIP_P2P_UNFUSED");
     for (int32_t e = 0; e < cfg->n_epochs; ++e) {
         const uint32_t epoch_ctr = update_ctr * (uint32_t)cfg->n_epochs + (uint32_t)e;
@@ -936,6 +969,7 @@ int32_t rlhip_ppo_update_comm_f32(int32_t kind, const rlhip_ppo_cfg* cfg, int64_
     int32_t rc = rlhip_comm_info(comm, &d);
     if (rc) return rc;
     RLHIP_REQUIRE(cfg != nullptr, "cfg is NULL");
+    RLHIP_REQUIRE(!(cfg->normalize_advantage && d.world > 1), "normalize_advantage is not supported with world > 1");
     if (d.world == 1 && !d.rccl_active)
         return rlhip_ppo_update_f32(kind, cfg, n, T, traj, params, m, v, beta_pow, seed, update_ctr, workspace, grad_scratch,
                                     losses_out, stream);
@@ -994,9 +1028,18 @@ static int32_t update_entry(int32_t kind, const rlhip_ppo_cfg* cfg, int64_t n, i
     bool first = true;
     for (int32_t e = 0; e < cfg->n_epochs; ++e) {
         uint32_t epoch_ctr = ctr ? (uint32_t)e : update_ctr * (uint32_t)cfg->n_epochs + (uint32_t)e;
+        const rlhip_ppo_traj* te = traj;
+        rlhip_ppo_traj tn;
+        if (cfg->normalize_advantage) {
+            // this epoch's normalised plane; the epoch's first gradient launch re-writes the sample records from it (the
+            // first-launch form below: unit records from `params`, the same bits as the patched image)
+            if (int32_t rcn = normalized_traj(kind, cfg, n, T, traj, seed, epoch_ctr, ctr, workspace, &tn, s)) return rcn;
+            te = &tn;
+            first = true;
+        }
         for (int32_t mb = 0; mb < cfg->n_microbatches; ++mb) {
             GradLaunch L;
-            int32_t rc = prepare_grad(kind, cfg, n, T, traj, params, seed, epoch_ctr, mb, workspace, &L, ctr);
+            int32_t rc = prepare_grad(kind, cfg, n, T, te, params, seed, epoch_ctr, mb, workspace, &L, ctr);
             if (rc) return rc;
             if (samples) L.g.samples = samples;
             if (first) {

@@ -672,6 +672,9 @@ function HipPPOPolicy(env::HipVecEnv; update_freq = 32, seed = env.seed, comm = 
     cfg = Ref(with_kwargs(c[]; continuous = is_continuous(env), kwargs...))
     np = ccall((:rlhip_ppo_nparams, LIB), Int64, (Int32, Ref{PPOCfg}), env.kind, cfg)
     np > 0 || chk(Int32(-1))
+    # per-rank advantage statistics would not be those of one GPU with a world-times larger batch (DESIGN.md section 6)
+    (cfg[].normalize_advantage != 0 && comm !== nothing && comm.world > 1) &&
+        throw(ArgumentError("HipPPOPolicy: normalize_advantage is not supported with a communicator of world > 1"))
     n, T, ns = env.n, Int(update_freq), obs_dim(env.kind)
     na = is_continuous(env) ? 1 : length(action_space(env))
     nout = is_continuous(env) ? 2na : na
@@ -777,6 +780,16 @@ function optimise!(p::HipPPOPolicy, ::PostActStage, env::HipVecEnv; fused_rollou
     p.update_ctr += 1
     p.n_pushed = 0
     true
+end
+
+"""The normalised advantages of micro-batch `mb` of epoch `epoch_ctr` -- what the gradient reads with
+`normalize_advantage = 1` (the removed Zoo PPO's `(A - mean) / clamp(std, 1e-8, 1000)`): `out` (T * n Float32 on the device,
+only that micro-batch's entries written) and `stats` (2 Float64 on the device: mean, std)."""
+function normalize_advantage!(out::DevBuf{Float32}, stats::DevBuf{Float64}, p::HipPPOPolicy, epoch_ctr::Integer, mb::Integer)
+    chk(ccall((:rlhip_ppo_adv_normalize_f32, LIB), Int32,
+              (Ref{PPOCfg}, Int64, Int64, Ptr{Cvoid}, UInt64, UInt32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              p.cfg, p.n, p.T, p.adv.ptr, p.seed, epoch_ctr, mb, out.ptr, stats.ptr, stream()))
+    out
 end
 
 # ------------------------------------------------------------------------------------------------------------------

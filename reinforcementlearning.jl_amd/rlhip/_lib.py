@@ -242,6 +242,7 @@ _PROTOS = {
                                     P(PPOTraj), vp]),
     "rlhip_ppo_gae_f32": (i32, [P(PPOCfg), i64, i64, P(PPOTraj), vp]),
     "rlhip_ppo_workspace_bytes": (i64, [i32, P(PPOCfg), i64, i64]),
+    "rlhip_ppo_adv_normalize_f32": (i32, [P(PPOCfg), i64, i64, vp, u64, u32, i32, vp, vp, vp]),
     "rlhip_ppo_workspace_init": (i32, [vp, i64, vp]),
     "rlhip_ppo_workspace_release": (i32, [vp]),
     "rlhip_ppo_grad_f32": (i32, [i32, P(PPOCfg), i64, i64, P(PPOTraj), vp, u64, u32, i32, vp, vp, vp,

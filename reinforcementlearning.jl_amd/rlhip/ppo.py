@@ -69,6 +69,13 @@ class PPOPolicy:
         self.env = env
         self.kind = env.kind
         self.cfg = make_ppo_cfg(continuous=int(env.continuous), **kw)
+        if self.cfg.normalize_advantage and process_group is not None:
+            import torch.distributed as dist
+
+            if dist.get_world_size(process_group) > 1:
+                # per-rank statistics would not be those of one GPU with a world-times larger batch
+                raise _lib.RLHipArgumentError("PPOPolicy: normalize_advantage is not supported with a process group of "
+                                              "world > 1")
         self.T = int(update_freq)
         self.seed = env.seed if seed is None else int(seed)
         dev = env.device
@@ -182,6 +189,17 @@ class PPOPolicy:
         call("rlhip_ppo_grad_fresh_f32" if records_fresh else "rlhip_ppo_grad_f32", self.kind, C.byref(self.cfg), self.trajectory.n, self.T,
              C.byref(self.trajectory.c), ptr(self.params), self.seed, epoch_ctr, mb, ptr(self.workspace),
              ptr(self.grad), ptr(self.losses), stream_ptr())
+
+    def normalize_advantage_(self, epoch_ctr, mb, out=None):
+        """The normalised advantages of micro-batch `mb` of epoch `epoch_ctr` (what the gradient reads with
+        normalize_advantage = 1): returns (out, stats) with out (T, n) float32 -- only that micro-batch's entries written,
+        a copy of adv by default -- and stats = float64 [mu, sd]."""
+        tr = self.trajectory
+        out = tr.adv.clone() if out is None else out
+        stats = torch.zeros(2, dtype=torch.float64, device=tr.adv.device)
+        call("rlhip_ppo_adv_normalize_f32", C.byref(self.cfg), tr.n, self.T, ptr(tr.adv), self.seed, epoch_ctr, mb, ptr(out),
+             ptr(stats), stream_ptr())
+        return out, stats
 
     def apply_(self, grad_scale=1.0):
         """[grad_scale] -> clip_by_global_norm! -> Adam -> weight-record refresh, one launch"""
