@@ -15,8 +15,9 @@ on both sides, whatever the summation order:
     accumulate) and the head is a dyadic rational that fits 24 bits -- relu nets produce bit-identical z1, h1, z2, h2, logits,
     mu, log sigma, V on the GPU and in the oracle (tanh nets: exact up to h1 = tanh(z1), where ocml and glibc differ by an ulp
     on some inputs; their layer-2 sums then differ in the last bits only);
-  * DQN: rewards are multiples of 1/4, gamma = 1/2, batch = 4096 = 2^12: TD targets, TD errors, the Huber branch (delta = 1,
-    BOTH branches occur) and dL/dq = e / batch are exact, so dz2 is bit-identical and rounds identically;
+  * DQN: rewards are multiples of 1/4, gamma = 1/2, batch = 4096 = 2^12 (and, at hidden = 128, 2^14 and 2^16: one batch per
+    gradient kernel of csrc/dqn3.hip): TD targets, TD errors, the Huber branch (delta = 1, BOTH branches occur) and
+    dL/dq = e / batch are exact, so dz2 is bit-identical and rounds identically;
   * PPO: log pi_old comes from the oracle's forward of the same parameters (ratio = 1 +- 1e-7: far from the clip edges),
     the advantage is +-2.5 with the sign of the action's direction and the return is V + 1 (coherent sums: no cancellation
     that would amplify f32 accumulation noise); dL/dlogits differs only by expf / logf ulps.
@@ -154,10 +155,23 @@ def test_ppo3_grad_tight(hidden, kind, cont, act):
 @pytest.mark.parametrize("ns,na", [(4, 2), (2, 3), (3, 3)])
 @pytest.mark.parametrize("hidden", [128, 256])
 def test_dqn3_grad_tight(hidden, ns, na, act):
+    _dqn3_grad_tight(hidden, ns, na, act, 4096)
+
+
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("ns,na", [(4, 2), (2, 3), (3, 3)])
+@pytest.mark.parametrize("batch", [16384, 65536])
+def test_dqn3_grad_tight_batches(batch, ns, na, act):
+    """hidden = 128 at the batches that reach the other two gradient forms (csrc/dqn3.hip): dqn3_grad_kernel (one 128-row tile
+    per workgroup, 8192 < batch < 65536) and dqn3_grad32_kernel<.., 2> (persistent, batch >= 65536); 4096 above is <.., 1>"""
+    _dqn3_grad_tight(128, ns, na, act, batch)
+
+
+def _dqn3_grad_tight(hidden, ns, na, act, batch):
     import rlhip
     from rlhip import dqn
 
-    batch, n_env, cap = 4096, 64, 80
+    n_env, cap = 64, 80
     rng = np.random.default_rng(100 * hidden + 10 * ns + act)
     traces = rlhip.CircularArraySARTSTraces(capacity=cap, n_env=n_env, obs_dim=ns)
     oring = oracle.Ring(cap, n_env, ns)
@@ -189,4 +203,5 @@ def test_dqn3_grad_tight(hidden, ns, na, act):
         y = r + gamma * (1 - t.astype(np.float32)) * qn.max(0)
         assert np.array_equal(tdh, np.abs(rq[a, np.arange(batch)] - y).astype(np.float32))
     assert abs(float(loss) - rl) <= 2e-6 * max(1.0, abs(rl))
-    _check(g.cpu().numpy(), rg, ns, hidden, na, f"dqn3{'w' if hidden == 256 else ''} ns={ns} na={na} act={act}", act == 0)
+    tag = f"dqn3{'w' if hidden == 256 else ''} ns={ns} na={na} act={act}" + ("" if batch == 4096 else f" batch={batch}")
+    _check(g.cpu().numpy(), rg, ns, hidden, na, tag, act == 0)
