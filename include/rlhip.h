@@ -411,6 +411,31 @@ int32_t rlhip_ring_sample_indices_nstep(const rlhip_ring* rb_host, int64_t batch
 int32_t rlhip_ring_fold_nstep(const rlhip_ring* rb_host, const int64_t* idx, int64_t batch, int32_t n_step, float gamma,
                               rlhip_ring* folded_host, int64_t* iota_out, rlhip_stream_t stream);
 
+/* Double DQN targets (`is_enable_double_DQN` of the removed DQNLearner) as a batch fold of the same shape.  For
+ * every flat logical index the record {s, a, r, t, s'} is read, a* = findmax(Q_online(s')) (first maximum wins,
+ * RLCore/src/utils/basic.jl:91-120), y = r + gamma_eff * (1 - t) * Qt(s')[a*], and {s, a, y, terminal = 1, s'} is written as record b
+ * of slot 0 of `folded` (the convention of rlhip_ring_fold_nstep: one stored vec-step of `batch` envs; iota_out, nullable, receives
+ * 0 .. batch - 1).  Every DQN gradient entry point then runs UNCHANGED on (folded, idx = iota_out) and computes the Double DQN update.
+ * Why that is exact: the target line of every gradient kernel (and of oracle/rlo_learn.c) is G = r + gamma * cont * mx with
+ * cont = 1 - terminal, built with -ffp-contract=off; with the reward field = y and terminal = 1 it gives G = y + 0 = y bit for bit,
+ * for any finite Qt(s') and whatever gamma the gradient call is given.
+ *   rlhip_dqn_fold_double_f32    two-layer nets (hidden a multiple of 4, <= 256; na <= 4; obs_dim 2..4: what rlhip_dqn_grad_*_f32
+ *                                takes).  One launch; `workspace` is unused (may be NULL).
+ *   rlhip_dqn3_fold_double_f32   three-layer bf16 MFMA nets (hidden 128 / 256, the (obs_dim, na) pairs of rlhip_dqn3_plan_f32): s'
+ *                                gathered into `workspace`, rlhip_dqn3_plan_f32 once per net, one select-and-write launch.
+ *   rlhip_dqn_double_workspace_bytes   bytes of `workspace` (layers = 2: 0; layers = 3: s' | Q(s') | Qt(s')); -1 on bad arguments.
+ * Record rings only.  `folded` may be the source ring itself when the source is an already folded ring and idx its iota -- the n-step
+ * form: rlhip_ring_fold_nstep first, then this fold in place with gamma_eff = rlhip_gamma_pow(gamma, n_step); every record is read and
+ * written by the same workgroup (two-layer) or lane (three-layer).  A -DRLHIP_BOUNDS_CHECK build validates idx first. */
+int64_t rlhip_dqn_double_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t batch, int32_t layers);
+int32_t rlhip_dqn_fold_double_f32(const rlhip_ring* rb_host, int64_t h, int64_t na, int32_t act, const float* params,
+                                  const float* target_params, const int64_t* idx, int64_t batch, float gamma_eff,
+                                  rlhip_ring* folded_host, int64_t* iota_out, void* workspace, rlhip_stream_t stream);
+int32_t rlhip_dqn3_fold_double_f32(const rlhip_ring* rb_host, int64_t h, int64_t na, int32_t act, const float* params,
+                                   const uint16_t* packed, const float* target_params, const uint16_t* target_packed,
+                                   const int64_t* idx, int64_t batch, float gamma_eff, rlhip_ring* folded_host, int64_t* iota_out,
+                                   void* workspace, rlhip_stream_t stream);
+
 /* Debugging aid ("a debug build that bounds-checks gather indices"; the reference's `traces[inds]` throws a
  * BoundsError): how many of the flat logical indices idx[0 .. batch) lie outside [0, length(trajectory) * n_env), and the position
  * of the first one (-1 if none).  One launch and a stream synchronisation: n_bad / first_bad are HOST pointers (first_bad may be

@@ -435,6 +435,38 @@ function sample_nstep!(t::HipTrajectory{Float32}, folded::HipTrajectory{Float32}
 end
 
 """
+    fold_double!(folded, iota, t, idx, net, tn, γ_eff; workspace = nothing) -> folded
+
+Double DQN targets (`is_enable_double_DQN` of the removed DQNLearner; SURVEY row L2) as a device fold: every record
+`(s, a, r, t, s′)` at the flat 0-based indices `idx` of `t` becomes `(s, a, y, true, s′)` in `folded` -- a
+`HipTrajectory(capacity = 1, n_env = length(idx), obs_dim = …)` -- with `y = r + γ_eff·(1−t)·Qₜ(s′)[findmax(Q(s′))]`.  The DQN gradient
+`ccall`s then take `folded.rb` and `iota` unchanged: their target line `r + γ·(1−terminal)·max Qₜ` gives `y + 0 = y` exactly.
+`folded === t` with `idx = iota` rewrites an n-step folded ring in place (`γ_eff = γⁿ` from `sample_nstep!`).  Three-layer networks
+need a `workspace` of `double_workspace_bytes(net, batch)` bytes.
+"""
+function fold_double!(folded::HipTrajectory{Float32}, iota::DevBuf{Int64}, t::HipTrajectory{Float32}, idx::DevBuf{Int64},
+                      net::HipApproximator, tn, γ_eff::Float32; workspace = nothing)
+    ws = workspace === nothing ? C_NULL : workspace.ptr
+    if net.layers == 2
+        chk(ccall((:rlhip_dqn_fold_double_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ref{Ring}, Ptr{Cvoid},
+                   Ptr{Cvoid}, Ptr{Cvoid}),
+                  t.rb, net.hidden, net.n_out, net.act, net.params.ptr, tn.target.ptr, idx.ptr, idx.n, γ_eff, folded.rb, iota.ptr,
+                  ws, stream()))
+    else
+        chk(ccall((:rlhip_dqn3_fold_double_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32,
+                   Ref{Ring}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                  t.rb, net.hidden, net.n_out, net.act, net.params.ptr, net.packed.ptr, tn.target.ptr, tn.target_packed.ptr,
+                  idx.ptr, idx.n, γ_eff, folded.rb, iota.ptr, ws, stream()))
+    end
+    folded
+end
+double_workspace_bytes(net::HipApproximator, batch::Integer) =
+    ccall((:rlhip_dqn_double_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64, Int32),
+          net.n_in, net.hidden, net.n_out, batch, net.layers)
+
+"""
     check_indices(t::HipTrajectory, idx::DevBuf{Int64}, n = length(idx)) -> (n_bad, first_bad)
 
 How many of the flat logical indices lie outside `1:length(t) * n_env` (0-based on the device), and the position of the first one
@@ -560,15 +592,23 @@ mutable struct HipDQNLearner <: AbstractLearner
     batchsize::Int; γ::Float32; δ::Float32; min_replay_history::Int; update_freq::Int; max_grad_norm::Float32
     seed::UInt64; draw_ctr::UInt32; n_updates::Int; vec_steps::Int
     grad::DevBuf{Float32}; loss::DevBuf{Float32}; workspace::DevBuf{UInt8}
+    # double_dqn (`is_enable_double_DQN` of the removed DQNLearner): the sampled batch is folded first (fold_double!), scratch below
+    double_dqn::Bool
+    folded::Union{Nothing,HipTrajectory{Float32}}; iota::Union{Nothing,DevBuf{Int64}}; td::Union{Nothing,DevBuf{Float32}}
+    double_workspace::Union{Nothing,DevBuf{UInt8}}
 end
 function HipDQNLearner(tn::HipTargetNetwork; batchsize = 32, γ = 0.99f0, huber_delta = 1f0, min_replay_history = 100,
-                       update_freq = 1, max_grad_norm = 0f0, seed = 0)
+                       update_freq = 1, max_grad_norm = 0f0, seed = 0, double_dqn = false)
     net = tn.network
     ws = net.layers == 2 ?
         ccall((:rlhip_dqn_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, net.n_out, batchsize) :
         ccall((:rlhip_dqn3_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, net.n_out, batchsize)
     HipDQNLearner(tn, batchsize, γ, huber_delta, min_replay_history, update_freq, max_grad_norm, UInt64(seed), UInt32(0), 0, 0,
-                  DevBuf{Float32}(net.params.n), DevBuf{Float32}(1), DevBuf{UInt8}(ws))     # zeroed workspace: ABI contract
+                  DevBuf{Float32}(net.params.n), DevBuf{Float32}(1), DevBuf{UInt8}(ws),     # zeroed workspace: ABI contract
+                  double_dqn,
+                  double_dqn ? HipTrajectory(capacity = 1, n_env = batchsize, obs_dim = net.n_in, batchsize = batchsize) : nothing,
+                  double_dqn ? DevBuf{Int64}(batchsize) : nothing, double_dqn ? DevBuf{Float32}(batchsize) : nothing,
+                  (double_dqn && net.layers == 3) ? DevBuf{UInt8}(double_workspace_bytes(net, batchsize)) : nothing)
 end
 forward(L::HipDQNLearner, x, batch) = forward(L.approximator, x, batch)
 
@@ -581,6 +621,7 @@ function optimise!(L::HipDQNLearner, ::PostActStage, t::HipTrajectory)
     # InsertSampleRatioController (the reference's `for batch in trajectory` draws a batch only when it allows one)
     (length(t) * t.rb.n_env >= L.min_replay_history && L.vec_steps % L.update_freq == 0 && on_sample!(t.controller)) || return false
     tn, net = L.approximator, L.approximator.network
+    L.double_dqn && return optimise_double!(L, t)
     if net.layers == 2
         chk(ccall((:rlhip_dqn_update_f32, LIB), Int32,
                   (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, UInt64, UInt32, Ptr{Cvoid},
@@ -607,6 +648,33 @@ function optimise!(L::HipDQNLearner, ::PostActStage, t::HipTrajectory)
         tn.n_optimise = 0
         repack!(net, tn.target, tn.target_packed)
     end
+    true
+end
+
+"the Double DQN form of optimise!: the draw of the plain form (same seed, same counter), fold_double!, the indexed gradient entry on
+the folded ring, then clip + Adam and the target sync through optimise!(tn, grad)"
+function optimise_double!(L::HipDQNLearner, t::HipTrajectory)
+    tn, net = L.approximator, L.approximator.network
+    chk(ccall((:rlhip_ring_sample_indices, LIB), Int32, (Ref{Ring}, Int64, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, L.batchsize, L.seed, L.draw_ctr, L.folded.idx.ptr, stream()))
+    fold_double!(L.folded, L.iota, t, L.folded.idx, net, tn, L.γ; workspace = L.double_workspace)
+    if net.layers == 2
+        chk(ccall((:rlhip_dqn_grad_idx_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32, Float32, Ptr{Cvoid},
+                   Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                  L.folded.rb, net.hidden, net.n_out, net.act, net.params.ptr, tn.target.ptr, L.batchsize, L.iota.ptr, L.γ, L.δ,
+                  L.workspace.ptr, L.grad.ptr, L.loss.ptr, L.td.ptr, stream()))
+    else
+        chk(ccall((:rlhip_dqn3_grad_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32,
+                   Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                  L.folded.rb, net.hidden, net.n_out, net.act, net.params.ptr, net.packed.ptr, tn.target.ptr,
+                  tn.target_packed.ptr, L.batchsize, L.iota.ptr, L.γ, L.δ, L.seed, L.draw_ctr, L.workspace.ptr, L.grad.ptr,
+                  L.loss.ptr, L.td.ptr, stream()))
+    end
+    L.draw_ctr += 1
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
     true
 end
 
@@ -1128,6 +1196,8 @@ function _run(agent::Agent{<:HipQBasedPolicy,<:HipTrajectory}, env::HipVecEnv{K,
     p, t = agent.policy, agent.trajectory
     L, tn = p.learner, p.learner.approximator
     net = tn.network
+    # rlhip_dqn_vec_step_f32 is plain DQN: a Double DQN learner runs on the per-stage loop above
+    L.double_dqn && return invoke(_run, Tuple{AbstractPolicy,HipVecEnv,Any,Any,Any}, agent, env, stop_condition, hook, reset_condition)
     push!(hook, PreExperimentStage(), agent, env)
     push!(agent, PreExperimentStage(), env)
     p.actions === nothing && (p.actions = DevBuf{Int32}(env.n); p.q = DevBuf{Float32}(net.n_out * env.n))

@@ -42,6 +42,8 @@ def _walk(obj, prefix, visit, seen, skip):
         path = f"{prefix}{name}"
         if any(s in path for s in skip) or name == "_backing":  # _backing: the allocation the env's arrays are views of
             continue
+        if getattr(type(v), "checkpoint_scratch", False):  # rewritten in full before every use (DoubleTargetFold): not state
+            continue
         if isinstance(v, torch.Tensor):
             visit("tensor", path, owner, key, v)
         elif isinstance(v, _SCALARS) or v is None:

@@ -244,9 +244,15 @@ class DQNLearner:
     per_beta = 0, the default, is the proportional-sampling variant without weights)."""
 
     def __init__(self, approximator, batchsize=32, gamma=0.99, huber_delta=1.0, min_replay_history=100,
-                 update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1):
+                 update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
+                 double_dqn=False):
         """n_step > 1: batches come from NStepBatchSampler(n_step, gamma, batchsize) -- the window folded on the device into one
-        transition -- and the TD target is R + gamma^n (1 - t) max Qt(s_{i+n}); uniform replay, per-stage loop."""
+        transition -- and the TD target is R + gamma^n (1 - t) max Qt(s_{i+n}); uniform replay, per-stage loop.
+        double_dqn = True (`is_enable_double_DQN` of the removed DQNLearner): the bootstrap value is Qt(s')[findmax(Q(s'))] instead of
+        max Qt(s').  Every per-stage update form folds its sampled batch first (DoubleTargetFold: the finished target y in the
+        reward field, terminal = 1) and runs the same gradient kernels on the folded ring; the fused vec-step stays plain DQN."""
+        self.double_dqn = bool(double_dqn)
+        self._double = None  # the DoubleTargetFold, made by the first folded update (a checkpoint carries the flag, not the scratch)
         self.n_step = int(n_step)
         self._nstep = None
         if self.n_step > 1:
@@ -294,6 +300,8 @@ class DQNLearner:
         if not self.should_update_(trajectory):
             return False
         net = self.approximator.network
+        if self.double_dqn:
+            return self._optimise_double_(traces, prioritized)
         if self._nstep is not None:
             if prioritized:
                 raise NotImplementedError("n-step targets: uniform replay only")
@@ -345,6 +353,54 @@ class DQNLearner:
         else:
             dqn_grad(traces, net.hidden, net.n_out, net.act, net.params, self.approximator.target, self.batchsize,
                      self.gamma, self.delta, self.seed, self.draw_ctr, self.workspace, self.grad, self.loss)
+        return self._exchange_and_apply_()
+
+    def _optimise_double_(self, traces, prioritized):
+        """optimise! with Double DQN targets: the batch every form samples (same draws, same keys) is folded, then the `_idx` /
+        `_idx_w` / dqn3 gradient entry runs on the folded ring with its iota.  td = |Q(s, a) - y| goes back under the ORIGINAL keys."""
+        tn = self.approximator
+        net = tn.network
+        if self._double is None:  # also the learner built without the flag that loaded a double_dqn = True checkpoint
+            from .trajectory import DoubleTargetFold
+
+            self._double = DoubleTargetFold()
+        gamma, in_place, weights = self.gamma, False, None
+        if self._nstep is not None:
+            if prioritized:
+                raise NotImplementedError("n-step targets: uniform replay only")
+            src, idx = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
+            gamma, in_place = self._nstep.gamma_n, True  # the n-step ring is rewritten in place, gamma^n as the discount
+        elif prioritized:
+            src = traces
+            idx, self._key, self._prio = traces.sample_prioritized(self.batchsize, self.seed, self.draw_ctr)
+            beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
+            if beta > 0.0:
+                call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
+                weights = self.is_weights
+        else:  # the draw rlhip_dqn_grad_f32 evaluates inline: the flag does not change which transitions are sampled
+            src, idx = traces, traces.sample_indices(self.batchsize, self.seed, self.draw_ctr)
+        self._idx = idx
+        folded, iota = self._double.fold(src, None if in_place else idx, net, tn.target, tn.target_packed, gamma, in_place)
+        if net.layers == 3:
+            if weights is not None:
+                call("rlhip_dqn3_grad_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
+                     ptr(tn.target), ptr(tn.target_packed), self.batchsize, ptr(iota), ptr(weights), gamma, self.delta,
+                     ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
+            else:
+                dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, tn.target, tn.target_packed,
+                          self.batchsize, gamma, self.delta, self.seed, self.draw_ctr, iota, self.workspace, self.grad, self.loss,
+                          self.td)
+        elif weights is not None:
+            call("rlhip_dqn_grad_idx_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(iota), ptr(weights), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
+                 ptr(self.td), stream_ptr())
+        else:
+            call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(iota), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td),
+                 stream_ptr())
+        if prioritized:  # trajectory[:priority, keys] = (|td| + eps)^alpha  (PrioritizedDQN write-back)
+            call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
+            traces.set_priority_(self._key, self.td)
         return self._exchange_and_apply_()
 
     def _exchange_and_apply_(self):

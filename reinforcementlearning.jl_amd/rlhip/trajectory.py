@@ -279,6 +279,53 @@ class NStepBatchSampler:
         return dict(state=s, action=a + 1, reward=r, terminal=t.view(torch.bool), next_state=sn)
 
 
+class DoubleTargetFold:
+    """Double DQN targets as a device fold (rlhip_dqn_fold_double_f32 / rlhip_dqn3_fold_double_f32, include/rlhip.h): every sampled
+    record {s, a, r, t, s'} becomes {s, a, y = r + gamma_eff (1 - t) Qt(s')[findmax(Q(s'))], terminal = 1, s'} in a batch-sized
+    record ring, on which every DQN gradient entry point computes the Double DQN update unchanged (its target line gives y + 0).
+    Owns the folded ring, the iota and the workspace, as NStepBatchSampler owns its own.  `fold(ring, None, ..., in_place=True)`
+    rewrites an already folded ring (the n-step form, gamma_eff = gamma^n) record by record: it takes no indices, because any
+    order but 0, 1, .., n_env - 1 would have workgroups read records that others are rewriting."""
+
+    checkpoint_scratch = True  # rlhip/checkpoint.py: the folded ring is rewritten by every fold, a checkpoint does not hold it
+
+    def __init__(self):
+        self._folded = self._iota = self._own_iota = self._ws = None
+        self._ws_key = None
+
+    def fold(self, traces, idx, network, target, target_packed, gamma_eff, in_place=False):
+        """-> (folded traces, iota); `network` is a HipApproximator (2 or 3 layers), `target` / `target_packed` its target copy"""
+        if in_place:
+            if idx is not None:
+                raise ValueError("the in-place fold walks the ring's own records 0 .. n_env - 1: pass idx = None")
+            b, dev = traces.n_env, traces.state.device
+            if self._own_iota is None or self._own_iota.numel() != b or self._own_iota.device != dev:
+                self._own_iota = torch.arange(b, dtype=torch.int64, device=dev)
+            folded, iota = traces, self._own_iota
+            idx = iota
+        else:
+            b, dev = idx.numel(), idx.device
+            if self._folded is None or self._folded.n_env != b or self._folded.obs_dim != traces.obs_dim:
+                self._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=dev)
+                self._iota = torch.empty(b, dtype=torch.int64, device=dev)
+            folded, iota = self._folded, self._iota
+        key = (network.n_in, network.hidden, network.n_out, b, network.layers)
+        if self._ws_key != key:
+            nbytes = int(_lib.lib.rlhip_dqn_double_workspace_bytes(*key))
+            if nbytes < 0:
+                raise ValueError("rlhip_dqn_double_workspace_bytes: bad network / batch description")
+            self._ws, self._ws_key = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), key
+        ws = ptr(self._ws) if self._ws is not None else None
+        if network.layers == 3:
+            call("rlhip_dqn3_fold_double_f32", C.byref(traces.rb), network.hidden, network.n_out, network.act, ptr(network.params),
+                 ptr(network.packed), ptr(target), ptr(target_packed), ptr(idx), b, gamma_eff, C.byref(folded.rb), ptr(iota), ws,
+                 stream_ptr())
+        else:
+            call("rlhip_dqn_fold_double_f32", C.byref(traces.rb), network.hidden, network.n_out, network.act, ptr(network.params),
+                 ptr(target), ptr(idx), b, gamma_eff, C.byref(folded.rb), ptr(iota), ws, stream_ptr())
+        return folded, iota
+
+
 class InsertSampleRatioController:
     """InsertSampleRatioController(ratio, threshold; n_inserted = 0, n_sampled = 0): sampling is allowed
     once n_inserted >= threshold and while n_sampled <= (n_inserted - threshold) * ratio
