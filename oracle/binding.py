@@ -728,6 +728,28 @@ def ppo_rollout(env, T, cfg, params, traj, vec_step0):
                                      C.c_uint32(vec_step0), C.byref(traj.c))
 
 
+def ppo_rollout_noise(seed, env_id_base, n, steps, k=0):
+    """The standard normal that rlo_ppo_rollout_f32 draws for action component k of env env_id_base + i at each vec-step of
+    `steps`: element k & 1 of rlo_normal_pair_f32 on words 0, 1 of Philox (seed, env_id_base + i, k / 2, step, NORMAL).
+    Returns float32 (len(steps), n)."""
+    ph, pair = lib().rlo_philox4x32_10, lib().rlo_normal_pair_f32
+    ph.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    pair.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    w = (C.c_uint32 * 4)()
+    z = (C.c_float * 2)()
+    z0, z1 = C.cast(z, C.POINTER(C.c_float)), C.cast(C.byref(z, 4), C.POINTER(C.c_float))
+    out = np.empty((len(steps), n), np.float32)
+    blk, odd, tag = k // 2, k & 1, TAG["NORMAL"]
+    for j, step in enumerate(steps):
+        row = out[j]
+        step = int(step) & 0xFFFFFFFF
+        for i in range(n):
+            ph(seed, (env_id_base + i) & 0xFFFFFFFF, blk, step, tag, w)
+            pair(w[0], w[1], z0, z1)
+            row[i] = z[odd]
+    return out
+
+
 def ppo_gae(cfg, traj):
     lib().rlo_ppo_gae_f32(C.byref(cfg), C.c_int64(traj.n), C.c_int64(traj.T), C.byref(traj.c))
 

@@ -3,8 +3,9 @@
 One case per row of the table, the row's id in the test id.  The comparisons are against oracle/ (double accumulation,
 the reference's expression order), never GPU against GPU -- except the rollout rows, which compare the fused rollout with the
 per-step protocol bit for bit: that protocol's plan! kernel is the plan_wide / plan_scalar kernel of the same (NS, H, ACT),
-pinned to the oracle by the ppo_plan rows, and its env step and pushes are pinned by tests/test_gpu_parity.py, so the
-chain rollout -> per-step protocol -> oracle is closed.
+pinned to the oracle by the ppo_plan rows, and its env step and pushes are pinned by tests/test_gpu_parity.py.  That chain
+shares policy_noise, policy_select, env_step1 and env_reset1 between its two ends; every step of every rollout row against
+the oracle itself is tests/test_gpu_rollout_audit.py.
 
 The inputs are chosen so that an error is visible, and each case asserts it (the measured fractions are in the message):
 tanh nets have at least half the hidden pre-activations in |z| < 2 (tanh' not ~ 0), relu nets 10 % .. 90 % active units;
