@@ -436,6 +436,30 @@ int32_t rlhip_dqn3_fold_double_f32(const rlhip_ring* rb_host, int64_t h, int64_t
                                    const int64_t* idx, int64_t batch, float gamma_eff, rlhip_ring* folded_host, int64_t* iota_out,
                                    void* workspace, rlhip_stream_t stream);
 
+/* DuelingNetwork(base, val, adv) Q-networks (RLCore/src/utils/networks.jl:510-522: Q = val .+ adv .- mean(adv, dims = 1), `val` and
+ * `adv` single Dense layers) as a PARAMETER fold.  The combine is linear in the head: with
+ *     W2e[a, :] = Wval + Wadv[a, :] - mean_a'(Wadv[a', :]),   b2e[a] = bval + badv[a] - mean_a'(badv[a'])
+ * a plain Dense(h, na) head computes the dueling Q, so every plan / act / gradient / Double DQN fold entry point serves a dueling net
+ * UNCHANGED on the effective plain vector.  Why the gradient is exact: dL/dh = sum_a W2e[a, :] dQ_a is the same expression in both
+ * forms, so dW1, db1 and the hidden-layer gradients of the plain kernels are the dueling net's as they stand, and the head maps back by
+ * the chain rule, dWval = sum_a dW2e[a, :], dWadv[a, :] = dW2e[a, :] - mean_a'(dW2e[a', :]), the biases by the same two rules.  The fold
+ * perturbs Q at rounding level only (measured <= 4.3e-7 of max|Q|); Huber's gradient and the max target are continuous in Q.
+ * Flat dueling vector: [ plain layout (rlhip_mlp2_nparams / rlhip_mlp3_nparams) with (Wadv, badv) as its last Dense | Wval (h) |
+ * bval (1) ]; the last Dense is W (na x h, column-major) followed by b (na).  Arithmetic (Float32, no contraction, bit-exact against
+ * tests/dueling_ref.py): per hidden unit j the left-folded sum s = ((x0 + x1) + x2) + x3 over the na rows, mean = s / float(na) (a
+ * true division), W2e[a, j] = (Wval[j] + Wadv[a, j]) - mean; unfold: dWval[j] = s over the dW2e rows, dWadv[a, j] = dW2e[a, j] - s / na.
+ *   rlhip_dueling_nparams          plain nparams + h + 1 (-1 on bad arguments); layers = 2 or 3.
+ *   rlhip_dueling_fold_f32         one launch: copies everything in front of the head, writes the effective head.  (duel2, eff2):
+ *                                  an optional second net (the target), both NULL or both given.  eff != duel.
+ *   rlhip_dueling_unfold_grad_f32  one launch: copies the base gradients, writes dWadv, dbadv, dWval, dbval.
+ * 1 <= na <= 4, h >= 1; 16-byte copies when both pointers of a net are 16-byte aligned.  Optimiser state lives on the dueling vector:
+ * unfold -> clip + Adam on the dueling vector -> fold (-> rlhip_mlp3_pack_bf16; the hidden W2 is the same in both vectors). */
+int64_t rlhip_dueling_nparams(int64_t ns, int64_t h, int64_t na, int32_t layers);
+int32_t rlhip_dueling_fold_f32(const float* duel, float* eff, const float* duel2, float* eff2, int64_t ns, int64_t h, int64_t na,
+                               int32_t layers, rlhip_stream_t stream);
+int32_t rlhip_dueling_unfold_grad_f32(const float* grad_eff, float* grad_duel, int64_t ns, int64_t h, int64_t na, int32_t layers,
+                                      rlhip_stream_t stream);
+
 /* Debugging aid ("a debug build that bounds-checks gather indices"; the reference's `traces[inds]` throws a
  * BoundsError): how many of the flat logical indices idx[0 .. batch) lie outside [0, length(trajectory) * n_env), and the position
  * of the first one (-1 if none).  One launch and a stream synchronisation: n_bad / first_bad are HOST pointers (first_bad may be

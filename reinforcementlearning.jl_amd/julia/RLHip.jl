@@ -29,7 +29,7 @@ using Random, DomainSets
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, DevValues
+    HipPrioritizedTraces, HipStackFrames, DevValues, HipDuelingApproximator
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -502,6 +502,9 @@ mutable struct HipApproximator <: AbstractLearner
     params::DevBuf{Float32}; m::DevBuf{Float32}; v::DevBuf{Float32}; beta_pow::DevBuf{Float32}; gn::DevBuf{Float32}
     packed::Union{Nothing,DevBuf{UInt16}}     # layers == 3: bf16 MFMA fragments of the hidden x hidden layer
     lr::Float32; beta1::Float32; beta2::Float32; eps::Float32
+    # a DuelingNetwork (HipDuelingApproximator below): the trained dueling vector and the scratch of its gradient; `params` is then
+    # the EFFECTIVE plain vector every kernel reads, `m` / `v` have the dueling length.  `nothing` for a plain Q-network.
+    dueling::Union{Nothing,DevBuf{Float32}}; dueling_grad::Union{Nothing,DevBuf{Float32}}
 end
 function HipApproximator(n_in, hidden, n_out; layers = 2, act = 0, lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8,
                          seed = 0, net_id = 0)
@@ -518,7 +521,7 @@ function HipApproximator(n_in, hidden, n_out; layers = 2, act = 0, lr = 1f-3, be
     A = HipApproximator(n_in, hidden, n_out, layers, act, p, DevBuf{Float32}(np), DevBuf{Float32}(np),
                         to_dev!(DevBuf{Float32}(2), Float32[beta1, beta2]), DevBuf{Float32}(1),
                         layers == 3 ? DevBuf{UInt16}(ccall((:rlhip_mlp3_packed_elems, LIB), Int64, (Int64,), hidden)) : nothing,
-                        lr, beta1, beta2, eps)
+                        lr, beta1, beta2, eps, nothing, nothing)
     repack!(A)
     A
 end
@@ -547,12 +550,103 @@ end
 "optimise!(A, grad) = Flux.Optimise.update!(A.optimiser_state, A.model, grad)  flux_approximator.jl:46 (+ optional
 clip_by_global_norm!, RLCore/utils/basic.jl:19-29, and the 1 / world scale after a gradient all-reduce)"
 function optimise!(A::HipApproximator, grad::DevBuf{Float32}; clip_norm = 0f0, grad_scale = 1f0)
+    A.dueling === nothing || return optimise_dueling!(A, grad; clip_norm = clip_norm, grad_scale = grad_scale)
     chk(ccall((:rlhip_clip_adam_f32, LIB), Int32,
               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Float32,
                Float32, Ptr{Cvoid}, Ptr{Cvoid}),
               A.params.ptr, grad.ptr, A.m.ptr, A.v.ptr, A.beta_pow.ptr, A.params.n, grad_scale, clip_norm, A.lr, A.beta1,
               A.beta2, A.eps, A.gn.ptr, stream()))
     repack!(A)
+end
+
+# ------------------------------------------------------------------------------------------------------------------
+# DuelingNetwork(base, val, adv)  RLCore/src/utils/networks.jl:510-522:  Q = val .+ adv .- mean(adv, dims = 1), with `val` = Dense(h, 1)
+# and `adv` = Dense(h, na).  The combine is linear in the head, so it is folded into the PARAMETERS (csrc/dueling.hip):
+#   W2e[a, :] = Wval + Wadv[a, :] - mean(Wadv, dims = 1),  b2e likewise  ->  a plain Dense(h, na) head computes the dueling Q
+# and every plan / act / gradient / fold_double! call runs unchanged on the effective vector `A.params`.
+#
+# Flat dueling vector (device):   [ base tensors ... | Wadv (na x h) | badv (na) | Wval (h) | bval (1) ]
+# Flux.destructure(model)[1]:     [ base tensors ... | Wval (1 x h)  | bval (1)  | Wadv (na x h) | badv (na) ]   (fields base, val, adv)
+# i.e. the permutation swaps the two trailing blocks, of h + 1 and na * h + na elements; the base tensors keep their order, every
+# matrix is column-major on both sides.  `dueling_from_flux` / `dueling_to_flux` apply it on import and export.
+# ------------------------------------------------------------------------------------------------------------------
+"Flux.destructure order (base, val, adv) -> the flat dueling vector (base, adv, val)"
+function dueling_from_flux(θ::AbstractVector{Float32}, hidden::Integer, n_out::Integer)
+    nv, na = hidden + 1, n_out * hidden + n_out
+    nb = length(θ) - nv - na
+    vcat(θ[1:nb], θ[nb + nv + 1:end], θ[nb + 1:nb + nv])
+end
+"the flat dueling vector (base, adv, val) -> Flux.destructure order (base, val, adv)"
+function dueling_to_flux(p::AbstractVector{Float32}, hidden::Integer, n_out::Integer)
+    nv, na = hidden + 1, n_out * hidden + n_out
+    nb = length(p) - nv - na
+    vcat(p[1:nb], p[nb + na + 1:end], p[nb + 1:nb + na])
+end
+dueling_nparams(n_in, hidden, n_out, layers) =
+    ccall((:rlhip_dueling_nparams, LIB), Int64, (Int64, Int64, Int64, Int32), n_in, hidden, n_out, layers)
+"dueling vector -> effective plain vector, one launch; (duel2, eff2): an optional second net (the target) in the same launch"
+function fold_dueling!(eff::DevBuf{Float32}, duel::DevBuf{Float32}, n_in, hidden, n_out, layers; duel2 = nothing, eff2 = nothing)
+    chk(ccall((:rlhip_dueling_fold_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int32, Ptr{Cvoid}),
+              duel.ptr, eff.ptr, duel2 === nothing ? C_NULL : duel2.ptr, eff2 === nothing ? C_NULL : eff2.ptr, n_in, hidden, n_out,
+              layers, stream()))
+    eff
+end
+"gradient of the effective plain vector -> gradient of the dueling vector (the chain rule of the fold), one launch"
+function unfold_dueling_grad!(grad_duel::DevBuf{Float32}, grad_eff::DevBuf{Float32}, n_in, hidden, n_out, layers)
+    chk(ccall((:rlhip_dueling_unfold_grad_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int32, Ptr{Cvoid}),
+              grad_eff.ptr, grad_duel.ptr, n_in, hidden, n_out, layers, stream()))
+    grad_duel
+end
+"""
+    HipDuelingApproximator(model::DuelingNetwork; lr, beta1, beta2, eps) -> HipApproximator
+
+`model.base` is `Dense(ns, h, act)` or `Chain(Dense(ns, h, act), Dense(h, h, act))`, `model.val = Dense(h, 1)`, `model.adv = Dense(h, na)`
+(single Dense heads; relu or tanh).  The weights are imported in `Flux.destructure` order and permuted (see above);
+`to_flux(A)` exports them the same way.  `A.params` is the effective plain vector, `A.dueling` the trained one.
+"""
+function HipDuelingApproximator(model::DuelingNetwork; lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8)
+    base = hasproperty(model.base, :layers) ? collect(model.base.layers) : [model.base]
+    length(base) in (1, 2) || throw(ArgumentError("DuelingNetwork base: one or two Dense layers"))
+    n_in, hidden = size(base[1].weight, 2), size(base[1].weight, 1)
+    size(model.val.weight) == (1, hidden) || throw(ArgumentError("DuelingNetwork val must be Dense(h, 1)"))
+    n_out = size(model.adv.weight, 1)
+    name = nameof(base[1].σ)
+    name in (:relu, :tanh) || throw(ArgumentError("activation must be relu or tanh"))
+    θ = Float32[]
+    for d in (base..., model.val, model.adv)
+        append!(θ, vec(d.weight)); append!(θ, d.bias)
+    end
+    HipDuelingApproximator(n_in, hidden, n_out, dueling_from_flux(θ, hidden, n_out); layers = length(base) + 1,
+                           act = name === :relu ? 0 : 1, lr = lr, beta1 = beta1, beta2 = beta2, eps = eps)
+end
+function HipDuelingApproximator(n_in::Integer, hidden::Integer, n_out::Integer, dueling::AbstractVector{Float32}; layers = 2, act = 0,
+                                lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8)
+    nd = dueling_nparams(n_in, hidden, n_out, layers)
+    length(dueling) == nd || throw(ArgumentError("the dueling vector has $(length(dueling)) elements, the network $nd"))
+    A = HipApproximator(n_in, hidden, n_out; layers = layers, act = act, lr = lr, beta1 = beta1, beta2 = beta2, eps = eps)
+    A.dueling = to_dev!(DevBuf{Float32}(nd), collect(dueling))
+    A.dueling_grad = DevBuf{Float32}(nd)
+    A.m, A.v = DevBuf{Float32}(nd), DevBuf{Float32}(nd)          # zeroed: Adam state of the dueling vector
+    refold!(A)
+    A
+end
+"A.params (and the bf16 fragments) from A.dueling"
+function refold!(A::HipApproximator)
+    fold_dueling!(A.params, A.dueling, A.n_in, A.hidden, A.n_out, A.layers)
+    repack!(A)
+end
+"the trained parameters in Flux.destructure order of DuelingNetwork(base, val, adv)"
+to_flux(A::HipApproximator) = A.dueling === nothing ? to_host(A.params) : dueling_to_flux(to_host(A.dueling), A.hidden, A.n_out)
+"unfold -> clip + Adam on the dueling vector (the global norm is the dueling gradient's, as Flux would take it) -> fold [-> pack]"
+function optimise_dueling!(A::HipApproximator, grad::DevBuf{Float32}; clip_norm = 0f0, grad_scale = 1f0)
+    unfold_dueling_grad!(A.dueling_grad, grad, A.n_in, A.hidden, A.n_out, A.layers)
+    chk(ccall((:rlhip_clip_adam_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Float32,
+               Float32, Ptr{Cvoid}, Ptr{Cvoid}),
+              A.dueling.ptr, A.dueling_grad.ptr, A.m.ptr, A.v.ptr, A.beta_pow.ptr, A.dueling.n, grad_scale, clip_norm, A.lr, A.beta1,
+              A.beta2, A.eps, A.gn.ptr, stream()))
+    refold!(A)
 end
 
 mutable struct HipTargetNetwork <: AbstractLearner      # TargetNetwork(network; sync_freq = 1, ρ = 0f0)  target_network.jl:27-60
@@ -562,11 +656,12 @@ mutable struct HipTargetNetwork <: AbstractLearner      # TargetNetwork(network;
     sync_freq::Int
     ρ::Float32
     n_optimise::Int
+    target_dueling::Union{Nothing,DevBuf{Float32}}      # a dueling network's target, as a dueling vector (`target` is its fold)
 end
 function HipTargetNetwork(network::HipApproximator; sync_freq = 1, ρ = 0f0)
     @assert 0 <= ρ <= 1 "ρ must in [0,1]"                # target_network.jl:50
     HipTargetNetwork(network, copy(network.params), network.packed === nothing ? nothing : copy(network.packed),
-                     sync_freq, ρ, 0)
+                     sync_freq, ρ, 0, network.dueling === nothing ? nothing : copy(network.dueling))
 end
 model(tn::HipTargetNetwork) = tn.network
 target(tn::HipTargetNetwork) = tn.target
@@ -576,8 +671,15 @@ function optimise!(tn::HipTargetNetwork, grad::DevBuf{Float32}; kw...)
     optimise!(tn.network, grad; kw...)
     tn.n_optimise += 1
     if tn.n_optimise % tn.sync_freq == 0
-        chk(ccall((:rlhip_polyak_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}),
-                  tn.target.ptr, tn.network.params.ptr, tn.target.n, tn.ρ, stream()))
+        net = tn.network
+        if net.dueling === nothing
+            chk(ccall((:rlhip_polyak_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}),
+                      tn.target.ptr, tn.network.params.ptr, tn.target.n, tn.ρ, stream()))
+        else     # Polyak on the dueling vectors, then the effective target again
+            chk(ccall((:rlhip_polyak_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}),
+                      tn.target_dueling.ptr, net.dueling.ptr, tn.target_dueling.n, tn.ρ, stream()))
+            fold_dueling!(tn.target, tn.target_dueling, net.n_in, net.hidden, net.n_out, net.layers)
+        end
         tn.n_optimise = 0
         repack!(tn.network, tn.target, tn.target_packed)
     end
@@ -622,6 +724,7 @@ function optimise!(L::HipDQNLearner, ::PostActStage, t::HipTrajectory)
     (length(t) * t.rb.n_env >= L.min_replay_history && L.vec_steps % L.update_freq == 0 && on_sample!(t.controller)) || return false
     tn, net = L.approximator, L.approximator.network
     L.double_dqn && return optimise_double!(L, t)
+    net.dueling === nothing || return optimise_dueling!(L, t)      # the fused update steps Adam on the vector its kernels read
     if net.layers == 2
         chk(ccall((:rlhip_dqn_update_f32, LIB), Int32,
                   (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, UInt64, UInt32, Ptr{Cvoid},
@@ -648,6 +751,29 @@ function optimise!(L::HipDQNLearner, ::PostActStage, t::HipTrajectory)
         tn.n_optimise = 0
         repack!(net, tn.target, tn.target_packed)
     end
+    true
+end
+
+"optimise! for a dueling network: the plain gradient entry (the draw of the fused update: same seed, same counter) on the effective
+vector, then unfold -> clip + Adam -> fold and the target sync through optimise!(tn, grad)"
+function optimise_dueling!(L::HipDQNLearner, t::HipTrajectory)
+    tn, net = L.approximator, L.approximator.network
+    if net.layers == 2
+        chk(ccall((:rlhip_dqn_grad_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, UInt64, UInt32, Ptr{Cvoid},
+                   Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                  t.rb, net.hidden, net.n_out, net.act, net.params.ptr, tn.target.ptr, L.batchsize, L.γ, L.δ, L.seed, L.draw_ctr,
+                  L.workspace.ptr, L.grad.ptr, L.loss.ptr, stream()))
+    else
+        chk(ccall((:rlhip_dqn3_grad_f32, LIB), Int32,
+                  (Ref{Ring}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32,
+                   Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                  t.rb, net.hidden, net.n_out, net.act, net.params.ptr, net.packed.ptr, tn.target.ptr, tn.target_packed.ptr,
+                  L.batchsize, C_NULL, L.γ, L.δ, L.seed, L.draw_ctr, L.workspace.ptr, L.grad.ptr, L.loss.ptr, C_NULL, stream()))
+    end
+    L.draw_ctr += 1
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
     true
 end
 
@@ -1198,6 +1324,8 @@ function _run(agent::Agent{<:HipQBasedPolicy,<:HipTrajectory}, env::HipVecEnv{K,
     net = tn.network
     # rlhip_dqn_vec_step_f32 is plain DQN: a Double DQN learner runs on the per-stage loop above
     L.double_dqn && return invoke(_run, Tuple{AbstractPolicy,HipVecEnv,Any,Any,Any}, agent, env, stop_condition, hook, reset_condition)
+    # ... and steps Adam on the vector its kernels read: a dueling network runs on the per-stage loop too
+    net.dueling === nothing || return invoke(_run, Tuple{AbstractPolicy,HipVecEnv,Any,Any,Any}, agent, env, stop_condition, hook, reset_condition)
     push!(hook, PreExperimentStage(), agent, env)
     push!(agent, PreExperimentStage(), env)
     p.actions === nothing && (p.actions = DevBuf{Int32}(env.n); p.q = DevBuf{Float32}(net.n_out * env.n))

@@ -10,7 +10,7 @@ from .core import (Agent, BatchStepsPerEpisode, ComposedHook, DeviceEpisodeStats
                    PPOAgent, RandomPolicy, StepsPerEpisode, StopAfterNEpisodes, StopAfterNSeconds,
                    StopAfterNSteps, StopIfAll, StopIfAny, TimePerStep, TotalBatchRewardPerEpisode, run,
                    run_fused_dqn, run_fused_ppo)
-from .dqn import (DQNLearner, EpsilonGreedyExplorer, GreedyExplorer, HipApproximator,  # noqa: F401
+from .dqn import (DQNLearner, DuelingApproximator, EpsilonGreedyExplorer, GreedyExplorer, HipApproximator,  # noqa: F401
                   QBasedPolicy, TargetNetwork)
 from .explorers import (BatchExplorer, GumbelSoftmaxExplorer, UCBExplorer, WeightedExplorer,  # noqa: F401
                         WeightedSoftmaxExplorer)

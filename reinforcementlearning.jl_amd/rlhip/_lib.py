@@ -175,6 +175,9 @@ _PROTOS = {
     "rlhip_dqn_double_workspace_bytes": (i64, [i64, i64, i64, i64, i32]),
     "rlhip_dqn_fold_double_f32": (i32, [P(Ring), i64, i64, i32, vp, vp, vp, i64, f32, P(Ring), vp, vp, vp]),
     "rlhip_dqn3_fold_double_f32": (i32, [P(Ring), i64, i64, i32, vp, vp, vp, vp, vp, i64, f32, P(Ring), vp, vp, vp]),
+    "rlhip_dueling_nparams": (i64, [i64, i64, i64, i32]),
+    "rlhip_dueling_fold_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, vp]),
+    "rlhip_dueling_unfold_grad_f32": (i32, [vp, vp, i64, i64, i64, i32, vp]),
     "rlhip_td_target_n_f32": (i32, [vp, i64, i64, i64, i64, vp, vp, f32, i32, vp, vp]),
     "rlhip_gamma_pow": (f32, [f32, i32]),
     "rlhip_ring_gather_is_frame_major": (i32, [P(Ring)]),

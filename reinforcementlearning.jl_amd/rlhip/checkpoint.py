@@ -6,6 +6,8 @@ Reference: no built-in checkpointing; the documented recipe is `JLD2.@save` of t
 trajectory and returns a FLAT {"path/to/field": numpy array or scalar} dict -- parameters, Adam moments and running
 beta powers, target network, env state and episode (RNG) counters, vec-step / update / sampler counters, ring-buffer
 storage with its head / length fields, sum-tree priorities -- which is what JLD2 (or np.savez) stores as is.
+A DuelingApproximator adds its trained vector and a dueling TargetNetwork its target (`.../dueling_params`,
+`.../target_dueling`, beside the effective `.../params` and `.../target` the kernels read; moments have the dueling length).
 `load_state_dict(obj, d)` copies it back IN PLACE (device pointers, captured graphs and C structs stay valid), after
 which the run continues bit-identically (tests/test_gpu_run.py).  Device <-> host copies go through torch here; the
 Julia glue uses rlhip_memcpy_d2h / rlhip_memcpy_h2d of the C ABI on the same buffers."""

@@ -385,6 +385,10 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
             or learner.process_group is not None or getattr(learner, "n_step", 1) != 1 or getattr(learner, "double_dqn", False):
         raise NotImplementedError("fused DQN step: plain eps-greedy, Float32 discrete env, uniform 1-step replay, 1 GPU, "
                                   "plain DQN targets (double_dqn=True runs on the per-stage loop)")
+    if getattr(net, "dueling_params", None) is not None:
+        # the fused vec-step steps Adam on the vector its kernels read; a dueling net trains another vector than the one they read
+        raise NotImplementedError("fused DQN step: plain Q-networks only; a DuelingApproximator (dueling_params) runs on the "
+                                  "per-stage loop, rlhip.run")
     stop_condition = stop_condition or StopAfterNSteps(1)
     hook = hook or EmptyHook()
     hook.push_(PRE_EXPERIMENT_STAGE, agent, env)

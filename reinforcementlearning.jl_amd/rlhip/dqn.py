@@ -200,8 +200,89 @@ class HipApproximator:
             mlp3_pack(self.params, self.n_in, self.hidden, self.n_out, self.packed)
 
 
+def dueling_nparams(n_in, h, n_out, layers=2):
+    return int(_lib.lib.rlhip_dueling_nparams(n_in, h, n_out, layers))
+
+
+def fold_dueling(duel, eff, n_in, h, n_out, layers, duel2=None, eff2=None):
+    """dueling vector(s) -> effective plain vector(s), one launch (csrc/dueling.hip); the second pair is the target net"""
+    call("rlhip_dueling_fold_f32", ptr(duel), ptr(eff), ptr(duel2), ptr(eff2), n_in, h, n_out, layers, stream_ptr())
+    return eff
+
+
+def unfold_dueling_grad(grad_eff, grad_duel, n_in, h, n_out, layers):
+    """gradient of the effective plain vector -> gradient of the dueling vector (chain rule of the fold), one launch"""
+    call("rlhip_dueling_unfold_grad_f32", ptr(grad_eff), ptr(grad_duel), n_in, h, n_out, layers, stream_ptr())
+    return grad_duel
+
+
+class _Scratch:
+    """a buffer rewritten in full before every use: not state of the path (rlhip/checkpoint.py leaves it out)"""
+    checkpoint_scratch = True
+
+    def __init__(self, t):
+        self.t = t
+
+
+class DuelingApproximator(HipApproximator):
+    """FluxApproximator(model = DuelingNetwork(base, val, adv), optimiser = Adam(lr))  RLCore/src/utils/networks.jl:510-522, with
+    `val = Dense(h, 1)` and `adv = Dense(h, n_out)`:  Q = val .+ adv .- mean(adv, dims = 1).
+
+    `.dueling_params` is the trained vector, [plain layout with (Wadv, badv) as its last Dense | Wval (h) | bval (1)]; `.m` / `.v`
+    have its length.  `.params` is the EFFECTIVE plain vector (rlhip_dueling_fold_f32) -- the one every kernel reads: plan, act,
+    gradient and the Double DQN fold run unchanged, and DQNLearner / QBasedPolicy / DoubleTargetFold need no edit.  optimise_ maps
+    the plain gradient back (rlhip_dueling_unfold_grad_f32), steps clip + Adam on the dueling vector (the global norm is the dueling
+    gradient's, as Flux would take it) and folds again.
+
+    A fresh val head is Glorot-uniform for Dense(h, 1), bias 0: Wval[j] = (2 u_j - 1) sqrt(6 / (h + 1)) with u from
+    rlhip_fill_uniform_f32(seed, t = net_id * 4 + 3, tag = 6 (INIT)) -- tensor id 3 of the net, beside the ids 0..2 that
+    rlhip_mlp2_init_f32 / rlhip_mlp3_init_f32 use.  `params` (a plain vector) seeds base and adv; `dueling_params` is the whole vector."""
+
+    def __init__(self, n_in, hidden, n_out, act="relu", lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0,
+                 net_id=0, device="cuda", params=None, layers=2, dueling_params=None):
+        if layers not in (2, 3):
+            raise ValueError("layers must be 2 or 3")
+        if not 1 <= n_out <= 4:
+            raise ValueError("the dueling fold takes 1..4 actions")
+        nd = dueling_nparams(n_in, hidden, n_out, layers)
+        if dueling_params is not None:
+            if params is not None:
+                raise ValueError("give params (a plain vector: base and adv) or dueling_params (the whole vector), not both")
+            duel = torch.as_tensor(dueling_params, dtype=torch.float32, device=device).clone()
+            if duel.numel() != nd:
+                raise ValueError(f"dueling_params has {duel.numel()} elements, the network {nd}")
+            params = duel[:nd - hidden - 1]  # the constructor below copies it; overwritten by the fold
+        super().__init__(n_in, hidden, n_out, act, lr, beta1, beta2, eps, seed, net_id, device, params, layers)
+        if dueling_params is None:
+            from .ops import fill_uniform
+
+            wval = (2.0 * fill_uniform(hidden, seed, net_id * 4 + 3, 6, device) - 1.0) * float((6.0 / (hidden + 1)) ** 0.5)
+            duel = torch.cat([self.params, wval, torch.zeros(1, dtype=torch.float32, device=device)])
+        self.dueling_params = duel.contiguous()
+        self.m = torch.zeros_like(self.dueling_params)
+        self.v = torch.zeros_like(self.dueling_params)
+        self._grad = _Scratch(torch.zeros_like(self.dueling_params))
+        self.refold_()
+
+    def refold_(self):
+        """.params (and .packed) from .dueling_params"""
+        fold_dueling(self.dueling_params, self.params, self.n_in, self.hidden, self.n_out, self.layers)
+        if self.layers == 3:
+            mlp3_pack(self.params, self.n_in, self.hidden, self.n_out, self.packed)
+
+    def optimise_(self, grad, clip_norm=0.0, grad_scale=1.0):
+        """`grad` is the gradient of `.params` as the plain kernels wrote it"""
+        from .ops import clip_adam_
+
+        g = unfold_dueling_grad(grad, self._grad.t, self.n_in, self.hidden, self.n_out, self.layers)
+        clip_adam_(self.dueling_params, g, self.m, self.v, self.beta_pow, grad_scale, clip_norm, self.lr, self.beta1,
+                   self.beta2, self.eps, self.gn)
+        self.refold_()
+
+
 class TargetNetwork:
-    """TargetNetwork(network; sync_freq = 1, ρ = 0f0)  target_network.jl:27-60."""
+    """TargetNetwork(network; sync_freq = 1, ρ = 0f0)  target_network.jl:27-60.  With a DuelingApproximator the target is kept as a
+    dueling vector too (`target_dueling`): Polyak runs on the dueling vectors and `target`, the effective vector, is folded again."""
 
     def __init__(self, network, sync_freq=1, rho=0.0):
         if not 0 <= rho <= 1:
@@ -209,6 +290,8 @@ class TargetNetwork:
         self.network, self.sync_freq, self.rho, self.n_optimise = network, int(sync_freq), float(rho), 0
         self.target = network.params.clone()
         self.target_packed = network.packed.clone() if getattr(network, "layers", 2) == 3 else None
+        if getattr(network, "dueling_params", None) is not None:
+            self.target_dueling = network.dueling_params.clone()
 
     def forward(self, x):
         return self.network.forward(x)
@@ -221,9 +304,13 @@ class TargetNetwork:
         self.network.optimise_(grad, **kw)
         self.n_optimise += 1
         if self.n_optimise % self.sync_freq == 0:
-            polyak_(self.target, self.network.params, self.rho)
-            self.n_optimise = 0
             net = self.network
+            if getattr(net, "dueling_params", None) is not None:
+                polyak_(self.target_dueling, net.dueling_params, self.rho)
+                fold_dueling(self.target_dueling, self.target, net.n_in, net.hidden, net.n_out, getattr(net, "layers", 2))
+            else:
+                polyak_(self.target, self.network.params, self.rho)
+            self.n_optimise = 0
             if getattr(net, "layers", 2) == 3:
                 mlp3_pack(self.target, net.n_in, net.hidden, net.n_out, self.target_packed)
 
