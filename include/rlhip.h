@@ -631,6 +631,53 @@ typedef struct {
 } rlhip_dqn_step_args;
 int32_t rlhip_dqn_vec_step_f32(rlhip_dqn_step_args* args, rlhip_stream_t stream);
 
+/* ------------------------- the same vec-step for folded learners (n-step, Double DQN, DuelingNetwork) -- */
+/* The folded batch of a two-layer learner in ONE launch: what the per-stage learner issues as
+ *     rlhip_ring_sample_indices[_nstep] -> rlhip_ring_fold_nstep (n_step > 1) -> rlhip_dqn_fold_double_f32 (double_dqn != 0)
+ * (`NStepBatchSampler` of RLTrajectories 0.4 and `is_enable_double_DQN` of the removed DQNLearner; see those entries above), byte for
+ * byte.  The lane that owns sample b draws its own flat logical start index (the Philox draw of rlhip_ring_sample_indices: same seed,
+ * draw_ctr and sample slot; written to idx_out when given), walks the window up to and including the first terminal step
+ * (R = discount_rewards_reduced, RLCore/src/utils/basic.jl:237-319, Float32, right to left; terminal = any(terminal); s' of the
+ * window's last record; n_step = 1 reproduces the stored record) and, with double_dqn, replaces the reward by
+ * y = R + gamma_eff * (1 - t) * Qt(s')[findmax(Q(s'))], gamma_eff = rlhip_gamma_pow(gamma, n_step), terminal = 1.  Record b of slot 0
+ * of `folded` (a record ring of n_env = batch, not the source) is written as one 64-byte line, iota_out[b] = b, and the counters of
+ * `folded` are set to "one stored vec-step".  With double_dqn == 0 the nets are not read: params / target_params may be NULL.
+ * Record rings, obs_dim 2..4, h a multiple of 4 and <= 256, na <= 4, n_step 1..32, batch >= 1, at least n_step stored steps;
+ * anything else is RLHIP_EINVAL before the launch.  The cost is a latency chain: n_step dependent record reads per sample, then the
+ * two forwards out of LDS on one CU per 64-sample tile. */
+int32_t rlhip_dqn_sample_fold_f32(const rlhip_ring* rb_host, int64_t batch, int32_t n_step, int32_t double_dqn, float gamma,
+                                  uint64_t seed, uint32_t draw_ctr, int64_t h, int64_t na, int32_t act, const float* params,
+                                  const float* target_params, rlhip_ring* folded_host, int64_t* idx_out, int64_t* iota_out,
+                                  rlhip_stream_t stream);
+
+/* One trip round the body of `_run` (RLCore/src/core/run.jl:52-70), as rlhip_dqn_vec_step_f32, for a learner whose batches are
+ * folded: n-step targets, Double DQN targets, a DuelingNetwork (RLCore/src/utils/networks.jl:510-522) or any combination.  plan! +
+ * act! + push! are those of rlhip_dqn_vec_step_f32.  optimise! (q_based_policy.jl:49) enqueues exactly what the per-stage learner
+ * computes: the folded batch (two layers: rlhip_dqn_sample_fold_f32; three: rlhip_ring_sample_indices[_nstep],
+ * rlhip_ring_fold_nstep, rlhip_dqn3_fold_double_f32, the latter in place on `folded` when n_step > 1), the unchanged gradient entry
+ * point on (folded, iota) with gamma^n, then flux_approximator.jl:46 and target_network.jl:70-88: clip + Adam [+ pack] and on
+ * do_sync Polyak [+ pack] -- for a dueling net unfold the gradient, clip + Adam on the dueling vector, fold it into base.params
+ * [+ pack], and on do_sync Polyak on target_dueling, fold into base.target [+ pack].  Results are bit-identical to the per-stage
+ * protocol.  With n_step == 1, double_dqn == 0 and a plain net the call IS rlhip_dqn_vec_step_f32(&base).  Every argument is
+ * checked before the first launch: a refused call moves no counter. */
+struct rlhip_dqn_fold_step_args_s { /* (a tagged struct with its typedef below: the first member is a struct, not a scalar) */
+    rlhip_dqn_step_args base;      /* every field as documented there */
+    int32_t n_step;                /* 1..32 */
+    int32_t double_dqn;            /* 0 / 1 */
+    rlhip_ring* folded;            /* record ring, capacity >= 1, n_env = base.batch; its counters are set to "one stored vec-step" */
+    int64_t* idx;                  /* i64[batch] scratch */
+    int64_t* iota;                 /* i64[batch] */
+    float* td;                     /* f32[batch], may be NULL */
+    void* fold_workspace;          /* rlhip_dqn_double_workspace_bytes(...) for layers == 3 && double_dqn; else may be NULL */
+    /* dueling (all NULL for a plain net): base.params / base.target are then the EFFECTIVE vectors, base.m / base.v /
+       base.beta_pow the Adam state of the DUELING vector */
+    float* dueling_params;
+    float* target_dueling;
+    float* grad_dueling;           /* f32[rlhip_dueling_nparams] */
+};
+typedef struct rlhip_dqn_fold_step_args_s rlhip_dqn_fold_step_args;
+int32_t rlhip_dqn_vec_step_fold_f32(rlhip_dqn_fold_step_args* args, rlhip_stream_t stream);
+
 /* ------------------------------------------------------ 3-layer Q-network on the MFMA -- */
 /* Chain(Dense(ns, 128, act), Dense(128, 128, act), Dense(128, na)) -- the blog's DQN model
  * (docs/homepage/blog/a_practical_introduction_to_RL.jl/index.html:15126-15128), forward(learner, x) =

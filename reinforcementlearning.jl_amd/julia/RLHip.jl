@@ -166,6 +166,19 @@ mutable struct DqnStepArgs   # rlhip_dqn_step_args
     workspace::Ptr{Cvoid}; grad::Ptr{Cvoid}; loss::Ptr{Cvoid}; gn::Ptr{Cvoid}; actions::Ptr{Cvoid}; q::Ptr{Cvoid}
     DqnStepArgs() = new()
 end
+mutable struct DqnFoldStepArgs   # rlhip_dqn_fold_step_args: `base` (rlhip_dqn_step_args) laid out in place, then the fold fields
+    kind::Int32; env_cfg::Ptr{Cvoid}; st::Ptr{Cvoid}; n::Int64; env_seed::UInt64; env_id_base::UInt32
+    obs::Ptr{Cvoid}; last_obs::Ptr{Cvoid}; ring::Ptr{Cvoid}; layers::Int32; h::Int64; na::Int64; act::Int32
+    params::Ptr{Cvoid}; packed::Ptr{Cvoid}; target::Ptr{Cvoid}; target_packed::Ptr{Cvoid}
+    m::Ptr{Cvoid}; v::Ptr{Cvoid}; beta_pow::Ptr{Cvoid}
+    lr::Float32; beta1::Float32; beta2::Float32; adam_eps::Float32; max_grad_norm::Float32; grad_scale::Float32
+    eps::Float64; explorer_seed::UInt64; explorer_step::UInt32; batch::Int64; gamma::Float32; huber_delta::Float32
+    sampler_seed::UInt64; draw_ctr::UInt32; do_update::Int32; do_sync::Int32; rho::Float32
+    workspace::Ptr{Cvoid}; grad::Ptr{Cvoid}; loss::Ptr{Cvoid}; gn::Ptr{Cvoid}; actions::Ptr{Cvoid}; q::Ptr{Cvoid}
+    n_step::Int32; double_dqn::Int32; folded::Ptr{Cvoid}; idx::Ptr{Cvoid}; iota::Ptr{Cvoid}; td::Ptr{Cvoid}
+    fold_workspace::Ptr{Cvoid}; dueling_params::Ptr{Cvoid}; target_dueling::Ptr{Cvoid}; grad_dueling::Ptr{Cvoid}
+    DqnFoldStepArgs() = new()
+end
 struct CommDesc         # rlhip_comm_desc
     rank::Int32; world::Int32; device::Int32; p2p_active::Int32; rccl_active::Int32
     seq::UInt32; cap::Int64; timeout_polls::Int64; status::Ptr{Cvoid}
@@ -698,19 +711,26 @@ mutable struct HipDQNLearner <: AbstractLearner
     double_dqn::Bool
     folded::Union{Nothing,HipTrajectory{Float32}}; iota::Union{Nothing,DevBuf{Int64}}; td::Union{Nothing,DevBuf{Float32}}
     double_workspace::Union{Nothing,DevBuf{UInt8}}
+    # n_step > 1 (NStepBatchSampler) and `fused`: `run` drives rlhip_dqn_vec_step_fold_f32, one ccall per vec-step (see `_run` below)
+    n_step::Int
+    fused::Bool
 end
 function HipDQNLearner(tn::HipTargetNetwork; batchsize = 32, γ = 0.99f0, huber_delta = 1f0, min_replay_history = 100,
-                       update_freq = 1, max_grad_norm = 0f0, seed = 0, double_dqn = false)
+                       update_freq = 1, max_grad_norm = 0f0, seed = 0, double_dqn = false, n_step = 1, fused = false)
     net = tn.network
+    @assert 1 <= n_step <= 32 "n_step must be in 1..32"
+    @assert n_step == 1 || fused "n-step targets run on the fused vec-step of this host: pass fused = true"
+    scratch = double_dqn || n_step > 1 || fused
     ws = net.layers == 2 ?
         ccall((:rlhip_dqn_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, net.n_out, batchsize) :
         ccall((:rlhip_dqn3_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, net.n_out, batchsize)
     HipDQNLearner(tn, batchsize, γ, huber_delta, min_replay_history, update_freq, max_grad_norm, UInt64(seed), UInt32(0), 0, 0,
                   DevBuf{Float32}(net.params.n), DevBuf{Float32}(1), DevBuf{UInt8}(ws),     # zeroed workspace: ABI contract
                   double_dqn,
-                  double_dqn ? HipTrajectory(capacity = 1, n_env = batchsize, obs_dim = net.n_in, batchsize = batchsize) : nothing,
-                  double_dqn ? DevBuf{Int64}(batchsize) : nothing, double_dqn ? DevBuf{Float32}(batchsize) : nothing,
-                  (double_dqn && net.layers == 3) ? DevBuf{UInt8}(double_workspace_bytes(net, batchsize)) : nothing)
+                  scratch ? HipTrajectory(capacity = 1, n_env = batchsize, obs_dim = net.n_in, batchsize = batchsize) : nothing,
+                  scratch ? DevBuf{Int64}(batchsize) : nothing, scratch ? DevBuf{Float32}(batchsize) : nothing,
+                  (double_dqn && net.layers == 3) ? DevBuf{UInt8}(double_workspace_bytes(net, batchsize)) : nothing,
+                  n_step, fused)
 end
 forward(L::HipDQNLearner, x, batch) = forward(L.approximator, x, batch)
 
@@ -1292,6 +1312,76 @@ function Base.push!(h::HipEpisodeStats, ::PostActStage, policy, env::HipVecEnv)
     nothing
 end
 
+"draw + n-step window + Double DQN target of a two-layer learner in ONE launch (rlhip_dqn_sample_fold_f32): byte for byte what
+rlhip_ring_sample_indices[_nstep] -> rlhip_ring_fold_nstep -> fold_double! leave in `folded` (NStepBatchSampler of RLTrajectories 0.4,
+`is_enable_double_DQN` of the removed DQNLearner); `idx` receives the drawn start indices, `iota` 0 .. batch - 1"
+function sample_fold!(folded::HipTrajectory, idx::DevBuf{Int64}, iota::DevBuf{Int64}, t::HipTrajectory, batch::Integer, n_step::Integer,
+                      double_dqn::Bool, γ, seed, draw_ctr, net::HipApproximator, tn::HipTargetNetwork)
+    chk(ccall((:rlhip_dqn_sample_fold_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Int32, Float32, UInt64, UInt32, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ring},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, batch, n_step, double_dqn ? 1 : 0, γ, seed, draw_ctr, net.hidden, net.n_out, net.act, net.params.ptr, tn.target.ptr,
+              folded.rb, idx.ptr, iota.ptr, stream()))
+    folded
+end
+
+"the loop body of `_run` (RLCore/src/core/run.jl:52-70) for a learner with folded batches -- n-step targets, Double DQN targets, a
+DuelingNetwork (RLCore/src/utils/networks.jl:510-522) -- as ONE ccall per vec-step (rlhip_dqn_vec_step_fold_f32).  The counters move as
+in the generic loop; while fewer than n_step steps are stored the vec-step counts, the controller is not asked and nothing is drawn
+(the n-step guard of rlhip/dqn.py optimise_)"
+function _run_folded(agent::Agent{<:HipQBasedPolicy,<:HipTrajectory}, env::HipVecEnv{K,Float32}, stop_condition, hook) where {K}
+    p, t = agent.policy, agent.trajectory
+    L, tn = p.learner, p.learner.approximator
+    net = tn.network
+    push!(hook, PreExperimentStage(), agent, env)
+    push!(agent, PreExperimentStage(), env)
+    p.actions === nothing && (p.actions = DevBuf{Int32}(env.n); p.q = DevBuf{Float32}(net.n_out * env.n))
+    a = DqnFoldStepArgs()
+    a.kind = env.kind; a.env_cfg = Base.unsafe_convert(Ptr{Cvoid}, env.cfg); a.st = Base.unsafe_convert(Ptr{Cvoid}, env.st)
+    a.n = env.n; a.env_seed = env.seed; a.env_id_base = env.env_id_base
+    a.obs = device_state(env).ptr; a.last_obs = env.last_obs.ptr; a.ring = pointer_from_objref(t.rb)
+    a.layers = net.layers; a.h = net.hidden; a.na = net.n_out; a.act = net.act
+    a.params = net.params.ptr; a.target = tn.target.ptr
+    a.packed = net.packed === nothing ? C_NULL : net.packed.ptr
+    a.target_packed = tn.target_packed === nothing ? C_NULL : tn.target_packed.ptr
+    a.m = net.m.ptr; a.v = net.v.ptr; a.beta_pow = net.beta_pow.ptr
+    a.lr = net.lr; a.beta1 = net.beta1; a.beta2 = net.beta2; a.adam_eps = net.eps
+    a.max_grad_norm = L.max_grad_norm; a.grad_scale = 1f0
+    a.explorer_seed = p.explorer_seed; a.batch = L.batchsize; a.gamma = L.γ; a.huber_delta = L.δ
+    a.sampler_seed = L.seed; a.rho = tn.ρ
+    a.workspace = L.workspace.ptr; a.grad = L.grad.ptr; a.loss = L.loss.ptr; a.gn = net.gn.ptr
+    a.actions = p.actions.ptr; a.q = p.q.ptr
+    a.n_step = L.n_step; a.double_dqn = L.double_dqn ? 1 : 0
+    a.folded = pointer_from_objref(L.folded.rb); a.idx = L.folded.idx.ptr; a.iota = L.iota.ptr; a.td = L.td.ptr
+    a.fold_workspace = L.double_workspace === nothing ? C_NULL : L.double_workspace.ptr
+    a.dueling_params = net.dueling === nothing ? C_NULL : net.dueling.ptr
+    a.target_dueling = net.dueling === nothing ? C_NULL : tn.target_dueling.ptr
+    a.grad_dueling = net.dueling === nothing ? C_NULL : net.dueling_grad.ptr
+    GC.@preserve a t env L begin
+        while true
+            a.eps = get_ϵ(p.explorer); a.explorer_step = UInt32(p.explorer.step); p.explorer.step += 1
+            on_insert!(t.controller, 1)
+            L.vec_steps += 1
+            frames = min(length(t) + 1, capacity(t))
+            a.do_update = (frames >= L.n_step && frames * env.n >= L.min_replay_history && L.vec_steps % L.update_freq == 0 &&
+                           on_sample!(t.controller)) ? 1 : 0
+            a.draw_ctr = L.draw_ctr
+            a.do_sync = (a.do_update == 1 && (tn.n_optimise + 1) % tn.sync_freq == 0) ? 1 : 0
+            chk(ccall((:rlhip_dqn_vec_step_fold_f32, LIB), Int32, (Ref{DqnFoldStepArgs}, Ptr{Cvoid}), a, stream()))
+            if a.do_update == 1
+                L.draw_ctr += 1; L.n_updates += 1
+                tn.n_optimise = a.do_sync == 1 ? 0 : tn.n_optimise + 1
+            end
+            push!(hook, PostActStage(), agent, env)
+            check!(stop_condition, agent, env) && break
+        end
+    end
+    env.obs_valid = true
+    push!(agent, PostExperimentStage(), env)
+    push!(hook, PostExperimentStage(), agent, env)
+    hook
+end
+
 # ------------------------------------------------------------------------------------------------------------------
 # run(policy, env, stop_condition, hook): ONE `_run` method for the vector env; RLCore/src/core/run.jl is untouched.
 # The MultiThreadEnv specialisation (blog index.md:351-374): no episode stages -- instances auto-reset in the kernel.
@@ -1322,6 +1412,8 @@ function _run(agent::Agent{<:HipQBasedPolicy,<:HipTrajectory}, env::HipVecEnv{K,
     p, t = agent.policy, agent.trajectory
     L, tn = p.learner, p.learner.approximator
     net = tn.network
+    # HipDQNLearner(...; fused = true): n-step, Double DQN and dueling learners as one ccall per vec-step
+    L.fused && return _run_folded(agent, env, stop_condition, hook)
     # rlhip_dqn_vec_step_f32 is plain DQN: a Double DQN learner runs on the per-stage loop above
     L.double_dqn && return invoke(_run, Tuple{AbstractPolicy,HipVecEnv,Any,Any,Any}, agent, env, stop_condition, hook, reset_condition)
     # ... and steps Adam on the vector its kernels read: a dueling network runs on the per-stage loop too

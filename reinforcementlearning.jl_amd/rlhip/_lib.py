@@ -84,6 +84,12 @@ class DqnStepArgs(C.Structure):
                 ("loss", vp), ("gn", vp), ("actions", vp), ("q", vp)]
 
 
+class DqnFoldStepArgs(C.Structure):
+    """rlhip_dqn_fold_step_args (include/rlhip.h)"""
+    _fields_ = [("base", DqnStepArgs), ("n_step", i32), ("double_dqn", i32), ("folded", vp), ("idx", vp), ("iota", vp),
+                ("td", vp), ("fold_workspace", vp), ("dueling_params", vp), ("target_dueling", vp), ("grad_dueling", vp)]
+
+
 class Ring(C.Structure):
     _fields_ = [(n, i64) for n in ("capacity", "n_env", "obs_dim", "head_sa", "len_sa", "head_rt",
                                    "len_rt")] + \
@@ -194,6 +200,8 @@ _PROTOS = {
                                   vp, vp]),
     "rlhip_dqn3_grad_w_f32": (i32, [P(Ring), i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp]),
     "rlhip_dqn_vec_step_f32": (i32, [vp, vp]),
+    "rlhip_dqn_sample_fold_f32": (i32, [P(Ring), i64, i32, i32, f32, u64, u32, i64, i64, i32, vp, vp, P(Ring), vp, vp, vp]),
+    "rlhip_dqn_vec_step_fold_f32": (i32, [vp, vp]),
     "rlhip_p2p_alloc": (i32, [i64, P(vp)]),
     "rlhip_p2p_free": (i32, [vp]),
     "rlhip_p2p_export": (i32, [vp, vp]),

@@ -438,6 +438,137 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
     return hook
 
 
+def _folded_update_gate(learner, trajectory, len_after):
+    """`do_update` of one fused vec-step for a learner with folded batches: DQNLearner.optimise_'s gate on the trajectory as the
+    step's push leaves it (`len_after` stored vec-steps).  While fewer than n_step steps are stored the vec-step counts, the
+    controller is not asked and no draw counter moves -- the per-stage learner's n-step guard."""
+    if getattr(learner, "_nstep", None) is not None and len_after < learner.n_step:
+        learner.vec_steps += 1
+        return False
+    return bool(learner.should_update_(trajectory, len_after * trajectory.container.n_env))
+
+
+def _folded_scratch(learner, traces, net):
+    """(folded ring, idx, iota, fold workspace or None): the scratch DQNLearner makes with its first folded update -- owned by the
+    same NStepBatchSampler / DoubleTargetFold objects, so a later rlhip.run on the agent finds what it would have made itself"""
+    from . import _lib
+    from .trajectory import CircularArraySARTSTraces, DoubleTargetFold
+
+    b, dev = learner.batchsize, traces.state.device
+    owner = learner._nstep
+    if learner.double_dqn:
+        if learner._double is None:
+            learner._double = DoubleTargetFold()
+        if owner is None:
+            owner = learner._double
+    if owner._folded is None or owner._folded.n_env != b or owner._folded.obs_dim != traces.obs_dim:
+        owner._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=dev)
+        owner._iota = torch.empty(b, dtype=torch.int64, device=dev)
+    idx = torch.empty(b, dtype=torch.int64, device=dev)
+    if learner.double_dqn:  # the per-stage Double DQN update leaves the indices its fold took in `_idx`: the draw, or the n-step iota
+        learner._idx = idx if learner._nstep is None else owner._iota
+    ws = None
+    if learner.double_dqn:
+        d = learner._double
+        if learner._nstep is not None and (d._own_iota is None or d._own_iota.numel() != b or d._own_iota.device != dev):
+            d._own_iota = torch.arange(b, dtype=torch.int64, device=dev)  # the in-place fold's index vector of the per-stage loop
+        key = (net.n_in, net.hidden, net.n_out, b, net.layers)
+        if d._ws_key != key:
+            nbytes = int(_lib.lib.rlhip_dqn_double_workspace_bytes(*key))
+            if nbytes < 0:
+                raise ValueError("rlhip_dqn_double_workspace_bytes: bad network / batch description")
+            d._ws, d._ws_key = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), key
+        ws = d._ws
+    return owner._folded, idx, owner._iota, ws
+
+
+def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
+    """`run_fused_dqn` for learners whose batches are folded: DQNLearner(n_step > 1), DQNLearner(double_dqn = True), a
+    DuelingApproximator, any combination -- and the plain learner.  The whole loop body is ONE C-ABI call per vec-step
+    (rlhip_dqn_vec_step_fold_f32): the kernels, their order and the counters are those of `run`, so parameters, optimiser state,
+    trajectory and explorer end bit-identical to the per-stage loop (tests/test_gpu_fused_folds.py) and either loop may continue
+    the other.  Prioritized traces, tie-breaking explorers, continuous / Float64 envs and a process group stay on `run`."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import call
+    from .ops import ptr, stream_ptr
+
+    policy, traj = agent.policy, agent.trajectory
+    learner, ex = policy.learner, policy.explorer
+    tn = learner.approximator
+    net = tn.network
+    traces = traj.container
+    if hasattr(traces, "sample_prioritized"):
+        raise NotImplementedError("fused folded DQN step: uniform replay only; prioritized traces (CircularPrioritizedTraces) run "
+                                  "on the per-stage loop, rlhip.run")
+    if ex.is_break_tie:
+        raise NotImplementedError("fused folded DQN step: plain eps-greedy only; a tie-breaking explorer (is_break_tie) runs on the "
+                                  "per-stage loop, rlhip.run")
+    if env.continuous or env.is_f64:
+        raise NotImplementedError("fused folded DQN step: Float32 discrete envs only; a continuous or Float64 env runs on the "
+                                  "per-stage loop, rlhip.run")
+    if learner.process_group is not None:
+        raise NotImplementedError("fused folded DQN step: 1 GPU; a learner with a process group (process_group) runs on the "
+                                  "per-stage loop, rlhip.run")
+    n_step, double = int(getattr(learner, "n_step", 1)), bool(getattr(learner, "double_dqn", False))
+    dueling = getattr(net, "dueling_params", None) is not None
+    stop_condition = stop_condition or StopAfterNSteps(1)
+    hook = hook or EmptyHook()
+    hook.push_(PRE_EXPERIMENT_STAGE, agent, env)
+    agent.push_(PRE_EXPERIMENT_STAGE, env)
+    dev = env.device
+    if policy._actions is None:
+        policy._actions = torch.empty(env.n, dtype=torch.int32, device=dev)
+        policy._q = torch.empty((net.n_out, env.n), dtype=torch.float32, device=dev)
+    f = _lib.DqnFoldStepArgs()
+    a = f.base
+    a.kind, a.env_cfg, a.st, a.n = env.kind, C.addressof(env.cfg), C.addressof(env._st), env.n
+    a.env_seed, a.env_id_base = env.seed, env.env_id_base
+    a.obs, a.last_obs = ptr(env.state()), ptr(env._last_obs)
+    a.ring = C.addressof(traces.rb)
+    a.layers, a.h, a.na, a.act = net.layers, net.hidden, net.n_out, net.act
+    a.params, a.target = ptr(net.params), ptr(tn.target)
+    a.packed = ptr(net.packed) if net.layers == 3 else None
+    a.target_packed = ptr(tn.target_packed) if net.layers == 3 else None
+    a.m, a.v, a.beta_pow = ptr(net.m), ptr(net.v), ptr(net.beta_pow)
+    a.lr, a.beta1, a.beta2, a.adam_eps = net.lr, net.beta1, net.beta2, net.eps
+    a.max_grad_norm, a.grad_scale = learner.max_grad_norm, 1.0
+    a.explorer_seed, a.batch, a.gamma, a.huber_delta = ex.seed, learner.batchsize, learner.gamma, learner.delta
+    a.sampler_seed, a.rho = learner.seed, tn.rho
+    a.workspace, a.grad, a.loss, a.gn = ptr(learner.workspace), ptr(learner.grad), ptr(learner.loss), ptr(net.gn)
+    a.actions, a.q = ptr(policy._actions), ptr(policy._q)
+    f.n_step, f.double_dqn, f.td = n_step, int(double), ptr(learner.td)
+    if n_step > 1 or double:
+        folded, idx, iota, ws = _folded_scratch(learner, traces, net)
+        f.folded, f.idx, f.iota = C.addressof(folded.rb), ptr(idx), ptr(iota)
+        f.fold_workspace = ptr(ws) if ws is not None else None
+    if dueling:
+        f.dueling_params, f.target_dueling, f.grad_dueling = ptr(net.dueling_params), ptr(tn.target_dueling), ptr(net._grad.t)
+    ctrl = traj.controller
+    s = stream_ptr()
+    while True:
+        a.eps, a.explorer_step = ex.get_eps(), ex.step
+        ex.step += 1
+        # the transition pushed by this call counts towards min_replay_history / the sample-ratio controller / the n-step guard
+        ctrl.on_insert_(1)
+        a.do_update = int(_folded_update_gate(learner, traj, min(len(traces) + 1, traces.capacity)))
+        a.draw_ctr = learner.draw_ctr
+        a.do_sync = int(a.do_update and (tn.n_optimise + 1) % tn.sync_freq == 0)
+        call("rlhip_dqn_vec_step_fold_f32", C.byref(f), s)
+        if a.do_update:
+            learner.draw_ctr += 1
+            learner.n_updates += 1
+            tn.n_optimise = 0 if a.do_sync else tn.n_optimise + 1
+        hook.push_(POST_ACT_STAGE, agent, env)
+        if stop_condition.check_(agent, env):
+            break
+    env._obs_valid = True
+    agent.push_(POST_EXPERIMENT_STAGE, env)
+    hook.push_(POST_EXPERIMENT_STAGE, agent, env)
+    return hook
+
+
 def run_fused_ppo(policy, env, n_updates, hook=None):
     """The same loop with the T-step rollout fused into one launch per update period (hooks see one
     PostActStage per period with the LAST step's reward / terminal flags)."""
