@@ -793,6 +793,38 @@ int32_t rlhip_ring_update_sample_gather_prioritized(const rlhip_ring* rb_host, f
                                                     void* s, int32_t* a, float* r, uint8_t* term, void* s_next,
                                                     uint32_t* sync, rlhip_stream_t stream);
 
+/* Prioritized n-step replay -- `sample(::NStepBatchSampler, ::CircularPrioritizedTraces)` of RLTrajectories 0.4 (un-vendored, PARITY
+ * UNPINNED): the priorities times a validity mask ("n_step transitions lie at or after this start"), drawn from the product.  Here
+ * the mask is kept in the tree: the leaves of the newest n_step - 1 transition frames are held at 0 and a frame receives its
+ * priority only once n_step transitions lie at or after it, so the unchanged rlhip_ring_sample_prioritized -- whose descent never
+ * enters a zero-sum subtree -- returns only valid window starts, distributed as p * valid / sum(p * valid).  Record rings only,
+ * n_step in 1..32.  (Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *   rlhip_ring_push_priority_nstep   after rlhip_ring_push_transition, in place of rlhip_ring_push_priority: first the n_env leaves of
+ *                                    the newest frame := 0 (after a wrap that slot still carries the overwritten transition's
+ *                                    priority), then, if length >= n_step, the n_env leaves of logical frame length - n_step :=
+ *                                    priority.  n_step = 1 leaves the tree of rlhip_ring_push_priority bit for bit.
+ *                                    n_step > capacity is RLHIP_EINVAL before anything moves.  Priorities written back with
+ *                                    rlhip_sumtree_update must go to keys drawn since the last push: a masked leaf is never drawn, so
+ *                                    it is never written.
+ *   rlhip_per_sample_fold_nstep_f32  the prioritized draw and the n-step window fold in ONE launch: the lane that owns sample b makes
+ *                                    the draw of rlhip_sumtree_sample, descends, maps the key to its logical index and walks the
+ *                                    window as rlhip_ring_fold_nstep does (up to and including the first terminal step, never past the
+ *                                    newest stored transition, right-to-left Float32 return); record b of slot 0 of `folded` is
+ *                                    written as a whole 64-byte line and the counters of `folded` are set to "one stored vec-step".
+ *                                    idx_out / key_out / prio_out / iota_out and the records are byte for byte those of
+ *                                    rlhip_ring_sample_prioritized followed by rlhip_ring_fold_nstep on the same tree.  key_out,
+ *                                    prio_out and iota_out may be NULL.  RLHIP_EINVAL when length < n_step (the masked tree has no
+ *                                    mass).  A -DRLHIP_BOUNDS_CHECK build has no index to validate here: the indices are produced
+ *                                    inside the launch (a key is clamped below capacity * n_env; every record read stays in the ring).
+ *                                    Every DQN gradient entry point then runs unchanged on (folded, iota_out) with
+ *                                    rlhip_gamma_pow(gamma, n_step), rlhip_dqn_fold_double_f32 / rlhip_dqn3_fold_double_f32 in place
+ *                                    before it for Double DQN. */
+int32_t rlhip_ring_push_priority_nstep(const rlhip_ring* rb_host, float* tree, float priority, int32_t n_step,
+                                       rlhip_stream_t stream);
+int32_t rlhip_per_sample_fold_nstep_f32(const rlhip_ring* rb_host, const float* tree, int64_t batch, int32_t n_step, float gamma,
+                                        uint64_t seed, uint32_t draw_ctr, int64_t* idx_out, int64_t* key_out, float* prio_out,
+                                        rlhip_ring* folded_host, int64_t* iota_out, rlhip_stream_t stream);
+
 /* ---------------------------------------------------------------------------------- MLP -- */
 /* Chain(Dense(n_in, h, act), Dense(h, n_out)) with flat parameters in Flux.destructure order:
  *   W1 (h x n_in col-major) | b1 (h) | W2 (n_out x h col-major) | b2 (n_out).   act: 0 relu, 1 tanh.

@@ -307,17 +307,6 @@ __global__ __launch_bounds__(64) void sumtree_update_small_kernel(float* tree, i
     sumtree_update_small_wave<false>(tree, P, logP, n_leaves, leaf, prio, n, sh);
 }
 
-__device__ __forceinline__ int64_t sumtree_descend(const float* __restrict__ tree, int64_t P, float v) {
-    int64_t node = 1;
-    while (node < P) {
-        float2 c = *reinterpret_cast<const float2*>(tree + 2 * node);
-        bool right = (v > c.x && c.y > 0.0f) || c.x == 0.0f;
-        if (right) v -= c.x;
-        node = 2 * node + (right ? 1 : 0);
-    }
-    return node - P;
-}
-
 // PrioritizedDQN write-back: p = (|td| + eps)^alpha; the power is evaluated in Float64 and rounded once
 __global__ __launch_bounds__(256) void per_priority_kernel(const float* __restrict__ td, int64_t n, float eps,
                                                            float alpha, float* __restrict__ out) {

@@ -1,5 +1,6 @@
 // sumtree_device.h -- the one-wavefront priority write-back (<= 64 keys) as a device function, shared by its own launch
-// (sumtree.hip: rlhip_sumtree_update) and by the prologue of the fused "update -> draw -> gather" launch (ring.hip, round 6).
+// (sumtree.hip: rlhip_sumtree_update) and by the prologue of the fused "update -> draw -> gather" launch (ring.hip, round 6); and the
+// descent of one prioritized draw.
 #pragma once
 #include "common.h"
 
@@ -14,6 +15,19 @@ struct SmallUpdateLds {
     float val[64];
     float sib[SMALL_MAXL][64];
 };
+
+// rand(rng, t)'s descent for one draw, `v <= left ? left : (v -= left; right)`, never into a zero-sum subtree while the sibling has
+// mass: log2(P) dependent 8-byte reads.  Shared by sumtree_sample_kernel (sumtree.hip) and the prioritized n-step launch (per_nstep.hip).
+__device__ __forceinline__ int64_t sumtree_descend(const float* __restrict__ tree, int64_t P, float v) {
+    int64_t node = 1;
+    while (node < P) {
+        float2 c = *reinterpret_cast<const float2*>(tree + 2 * node);
+        bool right = (v > c.x && c.y > 0.0f) || c.x == 0.0f;
+        if (right) v -= c.x;
+        node = 2 * node + (right ? 1 : 0);
+    }
+    return node - P;
+}
 
 // tree stores: plain when the kernel boundary publishes them (COHERENT = false: the stand-alone launch), device-scope write-through
 // when workgroups of the SAME launch read the tree afterwards (COHERENT = true: the fused launch; common.h's hand-off contract)

@@ -1084,6 +1084,30 @@ end
 sumtree_nodes(n_leaves) = ccall((:rlhip_sumtree_nodes, LIB), Int64, (Int64,), n_leaves)
 push_priority!(t::HipTrajectory, tree::DevBuf{Float32}, p::Float32) = chk(ccall((:rlhip_ring_push_priority, LIB), Int32,
     (Ref{Ring}, Ptr{Cvoid}, Float32, Ptr{Cvoid}), t.rb, tree.ptr, p, stream()))
+"""
+the same after a push into traces that serve an `NStepBatchSampler(n_step, …)` (`sample(::NStepBatchSampler, ::CircularPrioritizedTraces)`
+of RLTrajectories 0.4, whose validity mask is kept in the tree): the newest frame's leaves := 0, the leaves of the frame with `n_step`
+transitions at or after it := `p`.  The unchanged `sample_prioritized!` then returns only window starts.  `n_step = 1` is `push_priority!`.
+"""
+push_priority_nstep!(t::HipTrajectory, tree::DevBuf{Float32}, p::Float32, n_step::Integer) =
+    chk(ccall((:rlhip_ring_push_priority_nstep, LIB), Int32, (Ref{Ring}, Ptr{Cvoid}, Float32, Int32, Ptr{Cvoid}),
+              t.rb, tree.ptr, p, n_step, stream()))
+"""
+    sample_fold_prioritized!(folded, iota, idx, key, prio, t, tree, batch, n_step, γ, seed, ctr) -> γⁿ
+
+The prioritized draw on the masked tree and the n-step window fold in ONE launch (byte for byte `sample_prioritized!` followed by the
+fold of `sample_nstep!`): `folded` / `iota` go to the DQN gradient `ccall`s with the returned `γⁿ`, `key` to `set_priority!` -- before
+the next push, so that a masked leaf is never written -- and `prio` to `is_weights!`.  For Double DQN, `fold_double!` in place on `folded`.
+"""
+function sample_fold_prioritized!(folded::HipTrajectory{Float32}, iota::DevBuf{Int64}, idx::DevBuf{Int64}, key::DevBuf{Int64},
+                                  prio::DevBuf{Float32}, t::HipTrajectory{Float32}, tree::DevBuf{Float32}, batch::Integer,
+                                  n_step::Integer, γ::Float32, seed, ctr)
+    chk(ccall((:rlhip_per_sample_fold_nstep_f32, LIB), Int32,
+              (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ring}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              t.rb, tree.ptr, batch, n_step, γ, seed, ctr, idx.ptr, key.ptr, prio.ptr, folded.rb, iota.ptr, stream()))
+    ccall((:rlhip_gamma_pow, LIB), Float32, (Float32, Int32), γ, n_step)
+end
 "`inds, priorities = rand(rng, sumtree, batchsize)`: logical indices for the gather, physical keys for the write-back"
 sample_prioritized!(idx::DevBuf{Int64}, key::DevBuf{Int64}, prio::DevBuf{Float32}, t::HipTrajectory, tree, batch, seed, ctr) =
     chk(ccall((:rlhip_ring_sample_prioritized, LIB), Int32,
@@ -1181,11 +1205,13 @@ gaussian_logp!(logp::DevBuf{Float32}, mu::DevBuf{Float32}, raw_sigma::DevBuf{Flo
 # traces live on the device.  These are methods, not new entry points: each one forwards to a free function above.
 
 """
-    HipPrioritizedTraces(traces::HipTrajectory; default_priority = 100f0)
+    HipPrioritizedTraces(traces::HipTrajectory; default_priority = 100f0, n_step = 1)
 
 `CircularPrioritizedTraces(CircularArraySARTSTraces(...); default_priority)` of RLTrajectories 0.4 with the priorities in a
 device sum-tree: `push!` gives every new transition `default_priority`, `sample(traces, batchsize)` is the prioritized
 `BatchSampler` draw (`inds, priorities = rand(rng, sumtree, batchsize)`) and `traces[:priority, keys] = p` the write-back.
+`n_step > 1`: the traces serve an `NStepBatchSampler(n_step, …)` -- `push!` keeps the newest `n_step - 1` frames at priority 0
+(`push_priority_nstep!`), so every draw is a window start with its `n_step` transitions ahead.
 """
 mutable struct HipPrioritizedTraces
     traces::HipTrajectory
@@ -1194,18 +1220,24 @@ mutable struct HipPrioritizedTraces
     default_priority::Float32
     seed::UInt64
     draw_ctr::UInt32
+    n_step::Int
 end
-function HipPrioritizedTraces(t::HipTrajectory; default_priority = 100f0, seed = 0)
+function HipPrioritizedTraces(t::HipTrajectory; default_priority = 100f0, seed = 0, n_step = 1)
     default_priority > 0 || throw(ArgumentError("default_priority must be > 0"))
+    1 <= n_step <= min(32, t.rb.capacity) || throw(ArgumentError("n_step must be in 1..32 and no larger than the capacity"))
     n = Int(t.rb.capacity * t.rb.n_env)
-    HipPrioritizedTraces(t, DevBuf{Float32}(sumtree_nodes(n)), n, Float32(default_priority), UInt64(seed), UInt32(0))
+    HipPrioritizedTraces(t, DevBuf{Float32}(sumtree_nodes(n)), n, Float32(default_priority), UInt64(seed), UInt32(0), Int(n_step))
 end
 Base.length(p::HipPrioritizedTraces) = length(p.traces)
 Base.push!(p::HipPrioritizedTraces, x::NamedTuple{(:state,)}) = (push!(p.traces, x); p)
 "push!(traces, (state = s', action, reward, terminal)): the trajectory's push, then the new leaves := default_priority"
 function Base.push!(p::HipPrioritizedTraces, x::NamedTuple{(:state, :action, :reward, :terminal)})
     push!(p.traces, x)
-    push_priority!(p.traces, p.tree, p.default_priority)
+    if p.n_step == 1
+        push_priority!(p.traces, p.tree, p.default_priority)
+    else
+        push_priority_nstep!(p.traces, p.tree, p.default_priority, p.n_step)
+    end
     p
 end
 "the prioritized BatchSampler: (inds for the gather, keys for the write-back, priorities) as device buffers"

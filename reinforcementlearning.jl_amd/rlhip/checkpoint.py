@@ -5,7 +5,8 @@ Reference: no built-in checkpointing; the documented recipe is `JLD2.@save` of t
 :78-118).  With the state in HBM that hook needs an export: `state_dict(obj)` walks an env / policy / learner / agent /
 trajectory and returns a FLAT {"path/to/field": numpy array or scalar} dict -- parameters, Adam moments and running
 beta powers, target network, env state and episode (RNG) counters, vec-step / update / sampler counters, ring-buffer
-storage with its head / length fields, sum-tree priorities -- which is what JLD2 (or np.savez) stores as is.
+storage with its head / length fields, sum-tree priorities and the `n_step` of their window mask (checked against the traces it is
+loaded into: CircularPrioritizedTraces refuses a value its ring cannot serve) -- which is what JLD2 (or np.savez) stores as is.
 A DuelingApproximator adds its trained vector and a dueling TargetNetwork its target (`.../dueling_params`,
 `.../target_dueling`, beside the effective `.../params` and `.../target` the kernels read; moments have the dueling length).
 `load_state_dict(obj, d)` copies it back IN PLACE (device pointers, captured graphs and C structs stay valid), after

@@ -334,7 +334,9 @@ class DQNLearner:
                  update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
                  double_dqn=False):
         """n_step > 1: batches come from NStepBatchSampler(n_step, gamma, batchsize) -- the window folded on the device into one
-        transition -- and the TD target is R + gamma^n (1 - t) max Qt(s_{i+n}); uniform replay, per-stage loop.
+        transition -- and the TD target is R + gamma^n (1 - t) max Qt(s_{i+n}); per-stage loop.  Uniform replay, or
+        prioritized replay over CircularPrioritizedTraces(..., n_step = n_step): window starts drawn from the masked sum-tree and
+        folded in the same launch (rlhip_per_sample_fold_nstep_f32), priorities written back under the drawn keys.
         double_dqn = True (`is_enable_double_DQN` of the removed DQNLearner): the bootstrap value is Qt(s')[findmax(Q(s'))] instead of
         max Qt(s').  Every per-stage update form folds its sampled batch first (DoubleTargetFold: the finished target y in the
         reward field, terminal = 1) and runs the same gradient kernels on the folded ring; the fused vec-step stays plain DQN."""
@@ -380,18 +382,22 @@ class DQNLearner:
     def optimise_(self, trajectory):
         traces = trajectory.container
         prioritized = hasattr(traces, "sample_prioritized")
-        if self._nstep is not None and not prioritized and len(traces) < self.n_step:
-            # not one full window yet: the vec-step counts, the controller is not asked (no sample is drawn)
+        if self._nstep is not None and len(traces) < self.n_step:
+            # not one full window yet: the vec-step counts, the controller is not asked (no sample is drawn; over prioritized
+            # traces the masked tree has no mass yet)
             self.vec_steps += 1
             return False
+        if self._nstep is not None and prioritized and getattr(traces, "n_step", 1) != self.n_step:
+            raise ValueError(f"DQNLearner(n_step = {self.n_step}) needs CircularPrioritizedTraces(..., n_step = {self.n_step}): "
+                             f"these traces mask windows of {getattr(traces, 'n_step', 1)}")
         if not self.should_update_(trajectory):
             return False
         net = self.approximator.network
+        if self._nstep is not None and prioritized:
+            return self._optimise_per_nstep_(traces)
         if self.double_dqn:
             return self._optimise_double_(traces, prioritized)
         if self._nstep is not None:
-            if prioritized:
-                raise NotImplementedError("n-step targets: uniform replay only")
             folded, iota = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
             if net.layers == 3:
                 dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, self.approximator.target,
@@ -452,9 +458,7 @@ class DQNLearner:
 
             self._double = DoubleTargetFold()
         gamma, in_place, weights = self.gamma, False, None
-        if self._nstep is not None:
-            if prioritized:
-                raise NotImplementedError("n-step targets: uniform replay only")
+        if self._nstep is not None:  # (uniform replay: prioritized n-step batches take _optimise_per_nstep_)
             src, idx = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
             gamma, in_place = self._nstep.gamma_n, True  # the n-step ring is rewritten in place, gamma^n as the discount
         elif prioritized:
@@ -488,6 +492,48 @@ class DQNLearner:
         if prioritized:  # trajectory[:priority, keys] = (|td| + eps)^alpha  (PrioritizedDQN write-back)
             call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
             traces.set_priority_(self._key, self.td)
+        return self._exchange_and_apply_()
+
+    def _optimise_per_nstep_(self, traces):
+        """optimise! with n-step targets on prioritized traces (CircularPrioritizedTraces(n_step = n): window starts drawn from the
+        masked tree).  Draw + window fold in one launch, importance-sampling weights from the drawn priorities, the Double DQN fold in
+        place on the folded ring with gamma^n, the unchanged gradient entry on (folded, iota) with gamma^n, and (|td| + eps)^alpha
+        written back under the ORIGINAL keys -- in this call, before any further push, so a masked leaf is never written."""
+        tn = self.approximator
+        net = tn.network
+        smp = self._nstep
+        folded, iota, idx, self._key, self._prio = smp.sample_fold_prioritized(traces, self.draw_ctr)
+        self._idx = idx
+        gamma, weights = smp.gamma_n, None
+        beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
+        if beta > 0.0:
+            call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
+            weights = self.is_weights
+        if self.double_dqn:
+            if self._double is None:
+                from .trajectory import DoubleTargetFold
+
+                self._double = DoubleTargetFold()
+            folded, iota = self._double.fold(folded, None, net, tn.target, tn.target_packed, gamma, in_place=True)
+        if net.layers == 3:
+            if weights is not None:
+                call("rlhip_dqn3_grad_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
+                     ptr(tn.target), ptr(tn.target_packed), self.batchsize, ptr(iota), ptr(weights), gamma, self.delta,
+                     ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
+            else:
+                dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, tn.target, tn.target_packed,
+                          self.batchsize, gamma, self.delta, self.seed, self.draw_ctr, iota, self.workspace, self.grad, self.loss,
+                          self.td)
+        elif weights is not None:
+            call("rlhip_dqn_grad_idx_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(iota), ptr(weights), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
+                 ptr(self.td), stream_ptr())
+        else:
+            call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(iota), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td),
+                 stream_ptr())
+        call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
+        traces.set_priority_(self._key, self.td)
         return self._exchange_and_apply_()
 
     def _exchange_and_apply_(self):

@@ -139,10 +139,18 @@ CircularArraySARTSTraces.push_transition_maxpool_ = _push_transition_maxpool_
 class CircularPrioritizedTraces(CircularArraySARTSTraces):
     """CircularPrioritizedTraces(CircularArraySARTSTraces(...); default_priority): every pushed transition
     enters the device sum-tree with `default_priority`; `traces.set_priority_(keys, p)` is
-    `trajectory[:priority, keys] = p` (un-vendored RLTrajectories 0.4; sumtree.hip)."""
+    `trajectory[:priority, keys] = p` (un-vendored RLTrajectories 0.4; sumtree.hip).
 
-    def __init__(self, capacity, n_env=1, obs_dim=1, dtype=torch.float32, default_priority=100.0, device="cuda"):
+    n_step > 1 (record rings): the traces serve an NStepBatchSampler(n_step, ...).  The validity mask of RLTrajectories'
+    `sample(::NStepBatchSampler, ::CircularPrioritizedTraces)` is kept in the tree (rlhip_ring_push_priority_nstep, csrc/per_nstep.hip):
+    the newest n_step - 1 frames stay at priority 0 and a frame receives `default_priority` once n_step transitions lie at or after
+    it, so every draw is a window start with its n transitions ahead.  Write priorities back (`set_priority_`) under keys drawn since
+    the last push.  n_step = 1, the default, is the plain push."""
+
+    def __init__(self, capacity, n_env=1, obs_dim=1, dtype=torch.float32, default_priority=100.0, device="cuda", n_step=1):
+        self._check_n_step(n_step, capacity, dtype == torch.float32 and obs_dim <= 4)  # before anything is allocated
         super().__init__(capacity, n_env, obs_dim, dtype, device)
+        self.n_step = int(n_step)
         self.default_priority = float(default_priority)
         if not self.default_priority > 0.0:  # a tree without mass cannot be sampled (the draw would land on an empty slot)
             raise ValueError("default_priority must be > 0")
@@ -150,9 +158,30 @@ class CircularPrioritizedTraces(CircularArraySARTSTraces):
         nodes = int(_lib.lib.rlhip_sumtree_nodes(self.n_leaves))
         self.priorities = torch.zeros(nodes, dtype=torch.float32, device=self.state.device)  # zero-init contract
 
+    @staticmethod
+    def _check_n_step(n_step, capacity, records_layout):
+        if isinstance(n_step, bool) or int(n_step) != n_step or not 1 <= int(n_step) <= 32:
+            raise ValueError("n_step must be an integer in 1..32")
+        if int(n_step) > 1 and not records_layout:
+            raise ValueError("n_step > 1 needs a record ring (Float32 observations, obs_dim <= 4)")
+        if int(n_step) > capacity:
+            raise ValueError("n_step exceeds the capacity: no window would ever be complete")
+
+    def __setattr__(self, name, value):
+        # every assignment of the mask width is checked against the ring -- rlhip/checkpoint.py restores fields with setattr, so a
+        # checkpoint whose n_step these traces cannot serve is refused when it is loaded, not at the next push
+        if name == "n_step":
+            self._check_n_step(value, self.capacity, self.records_layout)
+            value = int(value)
+        super().__setattr__(name, value)
+
     def push_transition_(self, next_obs, action0, reward, terminal):
         super().push_transition_(next_obs, action0, reward, terminal)
-        call("rlhip_ring_push_priority", C.byref(self.rb), ptr(self.priorities), self.default_priority, stream_ptr())
+        if self.n_step == 1:
+            call("rlhip_ring_push_priority", C.byref(self.rb), ptr(self.priorities), self.default_priority, stream_ptr())
+        else:  # the newest frame := 0, the frame with n_step transitions at or after it := default_priority
+            call("rlhip_ring_push_priority_nstep", C.byref(self.rb), ptr(self.priorities), self.default_priority, self.n_step,
+                 stream_ptr())
 
     def sample_prioritized(self, batch, seed, draw_ctr):
         """-> (logical flat indices for gather, physical keys, priorities)"""
@@ -245,7 +274,9 @@ class NStepBatchSampler:
     indices with n transitions ahead of them, each window folded on the device into ONE transition
     (s_i, a_i, R = discount_rewards_reduced(r_i .. r_{i+ns-1}, gamma), any(terminal), s_{i+ns}) -- ns = n unless a terminal flag
     ends the window earlier.  `sample` returns the batch dictionary of BatchSampler; `fold` returns the folded record ring +
-    indices the DQN gradient entry points take unchanged (with gamma^n = `gamma_n` as their discount).  Record rings only."""
+    indices the DQN gradient entry points take unchanged (with gamma^n = `gamma_n` as their discount).  Record rings only.
+    Over CircularPrioritizedTraces(n_step = n) the starts are drawn in proportion to the masked priorities and the batch also carries
+    `key` and `priority`, as BatchSampler's does; traces built for another n_step are a ValueError."""
 
     def __init__(self, n, gamma, batchsize, seed=0):
         if not 1 <= int(n) <= 32:
@@ -253,30 +284,70 @@ class NStepBatchSampler:
         self.n, self.gamma, self.batchsize, self.seed, self.draw_ctr = int(n), float(gamma), int(batchsize), seed, 0
         self.gamma_n = float(_lib.lib.rlhip_gamma_pow(self.gamma, self.n))
         self._folded = None
+        self.key = self.priority = self._draw = None  # prioritized traces: keys / priorities of the last draw (+ the fused call's buffers)
+
+    def _prioritized(self, traces):
+        if not isinstance(traces, CircularPrioritizedTraces):
+            return False
+        if traces.n_step != self.n:
+            raise ValueError(f"the traces mask windows of n_step = {traces.n_step}, the sampler folds n = {self.n}: "
+                             "construct CircularPrioritizedTraces(..., n_step = n)")
+        return True
+
+    def _folded_ring(self, traces, b):
+        if self._folded is None or self._folded.n_env != b or self._folded.obs_dim != traces.obs_dim:
+            self._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=traces.state.device)
+            self._iota = torch.empty(b, dtype=torch.int64, device=traces.state.device)
+        return self._folded, self._iota
 
     def sample_indices(self, traces, draw_ctr=None):
+        """window starts: uniform over 1:(length - n + 1) per env; over CircularPrioritizedTraces(n_step = n) in proportion to the
+        masked priorities (the shipped prioritized draw), with `.key` / `.priority` of the draw kept on the sampler"""
         ctr = self.draw_ctr if draw_ctr is None else draw_ctr
+        if self._prioritized(traces):
+            if len(traces) < self.n:
+                raise _lib.RLHipArgumentError("the trajectory holds fewer than n transitions: the masked tree has no mass")
+            idx, self.key, self.priority = traces.sample_prioritized(self.batchsize, self.seed, ctr)
+            return idx
         idx = torch.empty(self.batchsize, dtype=torch.int64, device=traces.state.device)
         call("rlhip_ring_sample_indices_nstep", C.byref(traces.rb), self.batchsize, self.n, self.seed, ctr, ptr(idx), stream_ptr())
         return idx
 
+    def sample_fold_prioritized(self, traces, draw_ctr=None):
+        """the prioritized draw and the window fold in ONE launch (rlhip_per_sample_fold_nstep_f32; byte for byte sample_indices + fold)
+        -> (folded traces, iota, idx, key, priority)"""
+        if not self._prioritized(traces):
+            raise TypeError("sample_fold_prioritized takes CircularPrioritizedTraces(n_step = n)")
+        ctr = self.draw_ctr if draw_ctr is None else draw_ctr
+        b, dev = self.batchsize, traces.state.device
+        folded, iota = self._folded_ring(traces, b)
+        if self._draw is None or self._draw[0].numel() != b or self._draw[0].device != dev:
+            self._draw = (torch.empty(b, dtype=torch.int64, device=dev), torch.empty(b, dtype=torch.int64, device=dev),
+                          torch.empty(b, dtype=torch.float32, device=dev))
+        idx, self.key, self.priority = self._draw
+        call("rlhip_per_sample_fold_nstep_f32", C.byref(traces.rb), ptr(traces.priorities), b, self.n, self.gamma, self.seed, ctr,
+             ptr(idx), ptr(self.key), ptr(self.priority), C.byref(folded.rb), ptr(iota), stream_ptr())
+        return folded, iota, idx, self.key, self.priority
+
     def fold(self, traces, idx=None):
         """-> (folded traces: a CircularArraySARTSTraces of capacity 1 x batchsize envs holding the n-step transitions, iota)"""
         if idx is None:
+            if self._prioritized(traces):
+                folded, iota = self.sample_fold_prioritized(traces)[:2]
+                self.draw_ctr += 1
+                return folded, iota
             idx = self.sample_indices(traces)
             self.draw_ctr += 1
         b = idx.numel()
-        if self._folded is None or self._folded.n_env != b or self._folded.obs_dim != traces.obs_dim:
-            self._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=traces.state.device)
-            self._iota = torch.empty(b, dtype=torch.int64, device=traces.state.device)
-        call("rlhip_ring_fold_nstep", C.byref(traces.rb), ptr(idx), b, self.n, self.gamma, C.byref(self._folded.rb), ptr(self._iota),
-             stream_ptr())
-        return self._folded, self._iota
+        folded, iota = self._folded_ring(traces, b)
+        call("rlhip_ring_fold_nstep", C.byref(traces.rb), ptr(idx), b, self.n, self.gamma, C.byref(folded.rb), ptr(iota), stream_ptr())
+        return folded, iota
 
     def sample(self, traces):
         folded, iota = self.fold(traces)
         s, a, r, t, sn = folded.gather(iota)
-        return dict(state=s, action=a + 1, reward=r, terminal=t.view(torch.bool), next_state=sn)
+        extra = dict(key=self.key, priority=self.priority) if self._prioritized(traces) else {}
+        return dict(state=s, action=a + 1, reward=r, terminal=t.view(torch.bool), next_state=sn, **extra)
 
 
 class DoubleTargetFold:
