@@ -57,11 +57,14 @@ def test_maxpool_push_identity():
     s2 = torch.randint(0, 256, (d,), generator=g, dtype=torch.uint8).cuda()
     tr.push_state_maxpool_(s1, s2)
     stored.append(torch.maximum(s1, s2))
+    rewards = [0.25 * t - 1.0 for t in range(8)]  # exact in Float32, all different
+    terminals = [0, 1, 0, 0, 1, 1, 0, 1]
     for t in range(8):
         s1 = torch.randint(0, 256, (d,), generator=g, dtype=torch.uint8).cuda()
         s2 = torch.randint(0, 256, (d,), generator=g, dtype=torch.uint8).cuda()
         tr.push_transition_maxpool_(s1, s2, torch.tensor([t], dtype=torch.int32, device="cuda"),
-                                    torch.tensor([1.0], device="cuda"), torch.tensor([0], dtype=torch.uint8, device="cuda"))
+                                    torch.tensor([rewards[t]], device="cuda"),
+                                    torch.tensor([terminals[t]], dtype=torch.uint8, device="cuda"))
         stored.append(torch.maximum(s1, s2))
     assert len(tr) == cap
     idx = torch.arange(cap, device="cuda")
@@ -70,6 +73,7 @@ def test_maxpool_push_identity():
     for li in range(cap):
         assert torch.equal(s[li], stored[first + li]) and torch.equal(sn[li], stored[first + li + 1])
     assert a.tolist() == list(range(8 - cap, 8))
+    assert r.tolist() == rewards[8 - cap:] and t.tolist() == terminals[8 - cap:]  # the traces the fused kernel writes
 
 
 def test_stacked_gather_argument_validation():
