@@ -19,7 +19,8 @@
 //                         weights in registers for the whole T-step rollout; the <= 4 output sums are
 //                         combined by DPP adds inside the wavefront.  Two wavefronts per env group on one
 //                         SIMD: the actor wave runs the dependent chain (actor, selection, env step), the
-//                         critic wave everything else (critic, trajectory stores, sampling noise, GAE).
+//                         critic wave everything else (critic, trajectory stores, sampling noise, the
+//                         log-sum-exp of the two-action head's logp, GAE).
 //                         4096 envs x 16 lanes x 2 = 2048 wavefronts = two per SIMD of the chip; no
 //                         inter-workgroup communication at all (envs are independent while the weights
 //                         are frozen), so ONE launch covers T vec-steps.
@@ -38,6 +39,7 @@
 #include "env_device.h"
 #include "mlp_device.h"
 #include "select_device.h"
+#include "select_decide.h"
 #include "ppo_common.h"
 #include "ppo_sample_device.h"
 
@@ -67,6 +69,17 @@ __global__ void counters_advance_kernel(uint32_t* ctr, uint32_t d0, uint32_t d1)
 //                log / sqrt / sin / cos: depends on (env, step) only, one step per lane of the env's group -- same operations
 //                on the same operands as policy_sample), the bootstrap value and the GAE + returns scan
 // One workgroup barrier per vec-step hands the double-buffered step record over (the critic wave trails by one step).
+// Two-action head (HEAD == 2): the env step needs the ACTION, nothing in the rollout needs logp.  The actor wave decides the
+// action from the noise difference and the logit difference (select_decide.h: one Float32 and four Float64 instructions;
+// the log-sum-exp cancels out of the comparison up to four roundings, which a threshold bounds; the half of the rule that
+// depends on the noise alone is evaluated with the noise and travels in slots 2, 3 of its LDS entry) and runs the exact
+// selection behind a wave-uniform branch only when some lane is within the threshold of a tie (about one draw in 3e6) or
+// sees a non-finite operand.  The step record carries (a_best, d) where logp was; the critic wave keeps the pairs of the
+// last L steps in an LDS area of its own and, every L steps (and after the last one), lane `sub` of the env's group
+// evaluates se = 1 + exp(d), lse = log(se), logp = a_best - lse of ITS step -- the expressions of categorical_select1 on the
+// same operands, so the same bits -- and stores it: one issue of the Float64 exp + log serves L steps instead of one, off
+// the chain (47.1 -> 41.6 us at the headline shape, profiles/rollout_select.md).  RLHIP_ROLLOUT_SELECT_MARGIN multiplies
+// the threshold (inf: every draw takes the exact selection).
 // Measured (headline rollout, 4096 CartPole envs x T = 32, same box): one wave doing everything 64.0 us -> 60.4 us with the
 // head known at compile time -> 49.4 us split (profiles/r04_rollout.md).
 // NOA: actor outputs evaluated (2: two actions or (mu, log sigma); MAXO otherwise); the critic has one.
@@ -77,6 +90,18 @@ __global__ void counters_advance_kernel(uint32_t* ctr, uint32_t d0, uint32_t d1)
 // per-phase cycle sums of workgroup 0 (one actor wave, one critic wave), printed at the end of the launch: build with
 // RLHIP_EXTRA_FLAGS=-DRLHIP_ROLLOUT_TIMING (tools/rollout_one.py; proportions -- the stamps cost a few cycles each)
 #ifdef RLHIP_ROLLOUT_TIMING
+// wavefronts of ALL launches so far whose two-action decision went through the exact selection (printed with the actor wave's
+// phases; workgroups of the printing launch that are still running are counted in the next print)
+__device__ unsigned int g_rollout_exact_waves = 0;
+#define RT_COUNT_EXACT()                                                   \
+    do {                                                                   \
+        if ((threadIdx.x & 63) == 0) atomicAdd(&g_rollout_exact_waves, 1u); \
+    } while (0)
+#define RT_PRINT_EXACT()                                                                                              \
+    do {                                                                                                              \
+        if (blockIdx.x == 0 && threadIdx.x == 0)                                                                      \
+            printf("exact-selection wavefronts so far: %u\n", atomicAdd(&g_rollout_exact_waves, 0u));                  \
+    } while (0)
 #define RT_DECL long long rt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt_last_ = 0
 #define RT_START() rt_last_ = (long long)__builtin_amdgcn_s_memtime()
 #define RT_STAMP(k)                                                   \
@@ -94,6 +119,8 @@ __global__ void counters_advance_kernel(uint32_t* ctr, uint32_t d0, uint32_t d1)
                    rt_[5], rt_[6], rt_[7]);                                                                       \
     } while (0)
 #else
+#define RT_COUNT_EXACT()
+#define RT_PRINT_EXACT()
 #define RT_DECL
 #define RT_START()
 #define RT_STAMP(k)
@@ -105,7 +132,7 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
                                                                PolicyDesc pd, const float* __restrict__ params,
                                                                uint64_t seed, uint32_t env_id_base,
                                                                uint32_t vec_step0_in, const uint32_t* __restrict__ ctr, TrajPtrs tr,
-                                                               int store_state) {
+                                                               int store_state, float select_margin) {
     const uint32_t vec_step0 = vec_step0_in + (ctr ? ctr[0] : 0u);  // device-resident counter (graph replay)
     constexpr int NS = P::ODIM;
     constexpr int HPL = H / L;
@@ -126,7 +153,10 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
     const uint32_t id = env_id_base + (uint32_t)env;
 
     __shared__ double l_noise[2][EPB][NOISE_CH][MAXO];  // noise of two 16-step chunks (the critic wave fills the next one)
-    __shared__ float4 l_step[2][EPB][2];                // {x0..x3}, {logp, action bits, reward, terminal} of step t (t & 1)
+    // {x0..x3}, {logp, action bits, reward, terminal} of step t (t & 1); HEAD == 2: {a_best, d, action | terminal << 8, reward}
+    __shared__ float4 l_step[2][EPB][2];
+    // HEAD == 2: (a_best, d) of the last steps (L are kept), written and read by the critic wave alone
+    __shared__ float2 l_lse[HEAD == 2 ? EPB : 1][NOISE_CH];
 
     if (role == 0) {
         __builtin_amdgcn_s_setprio(3);  // the chain goes first whenever both waves of the SIMD are ready
@@ -139,13 +169,15 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
         e.episode = st.episode[env];
         float last_r = 0.0f;
         bool last_d = false;
+        [[maybe_unused]] const double sel_km = decide2_slope((double)select_margin);
         RT_DECL;
         __syncthreads();  // the noise of chunk 0
         RT_START();
         for (int t = 0; t < T; ++t) {
             double nz[MAXO];  // requested before the forward pass, consumed after it
 #pragma unroll
-            for (int k = 0; k < MAXO; ++k) nz[k] = (k < na) ? l_noise[(t / NOISE_CH) & 1][eg][t & (NOISE_CH - 1)][k] : 0.0;
+            for (int k = 0; k < MAXO; ++k)  // HEAD == 2: slots 2, 3 = the noise half of the decision rule
+                nz[k] = (HEAD == 2 ? k >= 2 : k < na) ? l_noise[(t / NOISE_CH) & 1][eg][t & (NOISE_CH - 1)][k] : 0.0;
             float x[4] = {0.f, 0.f, 0.f, 0.f};
             env_obs1(p, e, x);  // state(env) at PreActStage (post auto-reset)
             RT_STAMP(0);  // noise read issued + obs
@@ -154,20 +186,45 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
             RT_STAMP(1);  // actor forward
             int32_t ai;
             float af, lp;
-            policy_select(cont, na, oa, nz, ai, af, lp);
+            float sel_d = 0.0f;
+            if constexpr (HEAD == 2) {
+                // the action from the noise and the logit difference alone (select_decide.h); the log-sum-exp of logp has no
+                // consumer in the rollout and is evaluated by the critic wave, one step per lane, from (a_best, d)
+                float sel_e;
+                bool decided;
+                ai = decide2_logits(oa[0], oa[1], nz[2], nz[3], sel_km, &sel_e, &decided);
+                decide2_operands(oa[0], oa[1], sel_e, ai, &lp, &sel_d);  // lp = a_best
+                if (__builtin_amdgcn_ballot_w64(!decided) != 0) {  // wave-uniform; about one draw in 3e6
+                    RT_COUNT_EXACT();
+                    const double nzx[MAXO] = {l_noise[(t / NOISE_CH) & 1][eg][t & (NOISE_CH - 1)][0],
+                                              l_noise[(t / NOISE_CH) & 1][eg][t & (NOISE_CH - 1)][1], 0.0, 0.0};
+                    float lp_exact, xa0, xa1;
+                    const int32_t ax = categorical_select1(RegLogits{oa}, NoMask{}, na, NoiseRegs{nzx}, &lp_exact);
+                    if (!decided) ai = ax;
+                    select2_operands(oa[0], oa[1], &xa0, &xa1, &sel_d);  // any operands; the same bits where the rule decided
+                    lp = ai ? xa1 : xa0;
+                }
+                af = 0.0f;
+            } else {
+                policy_select(cont, na, oa, nz, ai, af, lp);
+            }
             RT_STAMP(2);  // selection
             env_step1(p, e, ai, af, last_r, last_d);
             if (last_d) env_reset1(p, e, seed, id);  // MultiThreadEnv auto-reset
             RT_STAMP(3);  // env step
             if (sub == 0) {
                 l_step[t & 1][eg][0] = make_float4(x[0], x[1], x[2], x[3]);
-                l_step[t & 1][eg][1] = make_float4(lp, cont ? af : __int_as_float(ai), last_r, last_d ? 1.0f : 0.0f);
+                if constexpr (HEAD == 2)
+                    l_step[t & 1][eg][1] = make_float4(lp, sel_d, __int_as_float(ai | (last_d ? 0x100 : 0)), last_r);
+                else
+                    l_step[t & 1][eg][1] = make_float4(lp, cont ? af : __int_as_float(ai), last_r, last_d ? 1.0f : 0.0f);
             }
             RT_STAMP(4);  // record
             __syncthreads();
             RT_STAMP(5);  // barrier
         }
         RT_PRINT("actor wave: obs/noise | forward | select | env step | record | barrier");
+        if (HEAD == 2) RT_PRINT_EXACT();
         {
             float x[4] = {0.f, 0.f, 0.f, 0.f};
             env_obs1(p, e, x);
@@ -192,6 +249,7 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
             for (int i = sub; i < NOISE_CH && c0 + i < T; i += L) {
                 double nz[MAXO] = {0.0, 0.0, 0.0, 0.0};
                 policy_noise(cont, na, seed, id, vec_step0 + (uint32_t)(c0 + i), nz);
+                if constexpr (HEAD == 2) decide2_noise_terms(nz[0], nz[1], (double)select_margin, &nz[2], &nz[3]);
 #pragma unroll
                 for (int k = 0; k < MAXO; ++k) l_noise[(c0 / NOISE_CH) & 1][eg][i][k] = nz[k];
             }
@@ -211,7 +269,33 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
             float oc[MAXO];
             net_forward<NS, HPL, L, ACT, 1>(C, x, oc);
             RT_STAMP(2);  // critic forward
-            if (writer) {
+            if constexpr (HEAD == 2) {
+                const float4 rec = l_step[t & 1][eg][1];
+                if (sub == 0) l_lse[eg][t & (NOISE_CH - 1)] = make_float2(rec.x, rec.y);
+                if (writer) {
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) tr.obs[((int64_t)t * NS + k) * n + env] = x[k];
+                    tr.value[(int64_t)t * n + env] = oc[0];
+                    const int aw = __float_as_int(rec.z);
+                    tr.action_i[(int64_t)t * n + env] = aw & 0xFF;
+                    tr.reward[(int64_t)t * n + env] = rec.w;
+                    tr.terminal[(int64_t)t * n + env] = (uint8_t)(aw >> 8);
+                }
+                // logp of the L steps that end here: one step per lane of the env's group (as fill_noise spreads a chunk: one issue
+                // of the Float64 exp + log serves L steps), the shipped expressions of categorical_select1 on the same operands --
+                // se, lse and lp bit for bit
+                if ((t & (L - 1)) == L - 1 || t + 1 == T) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // lane sub reads what lane 0 of its group wrote
+                    __builtin_amdgcn_wave_barrier();
+                    const int ts = (t & ~(L - 1)) + sub;
+                    const float2 ad = l_lse[eg][ts & (NOISE_CH - 1)];
+                    const float se = 1.0f + (float)::exp((double)ad.y);
+                    const float lse = (float)log_f64_sampling((double)se);
+                    if (active && ts <= t) tr.logp[(int64_t)ts * n + env] = ad.x - lse;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // ... before lane 0 overwrites it
+                    __builtin_amdgcn_wave_barrier();
+                }
+            } else if (writer) {
                 const float4 rec = l_step[t & 1][eg][1];
 #pragma unroll
                 for (int k = 0; k < NS; ++k) tr.obs[((int64_t)t * NS + k) * n + env] = x[k];
@@ -314,11 +398,18 @@ static int32_t rollout_impl(const typename P::cfg_t* cfg, const rlhip_env_state*
     P p = P::make(c2);
     EnvArrays<float> a = EnvArrays<float>::from(*st);
     TrajPtrs tr = TrajPtrs::from(*traj);
+    // RLHIP_ROLLOUT_SELECT_MARGIN (>= 1, read once): factor on the decision threshold of the two-action head; `inf` sends every
+    // draw through the exact selection -- no value changes a result bit (select_decide.h)
+    static const float select_margin = []() {
+        const char* e = getenv("RLHIP_ROLLOUT_SELECT_MARGIN");
+        return (e && e[0]) ? strtof(e, nullptr) : 1.0f;
+    }();
+    RLHIP_REQUIRE(select_margin >= 1.0f, "RLHIP_ROLLOUT_SELECT_MARGIN must be a number >= 1 (or inf)");
     // wide variant while the chip is not yet full of one-lane-per-env wavefronts
     bool wide = (pd.h == 256 || pd.h == 128 || pd.h == 64) && n * 16 <= (int64_t)1 << 22;
 #define LAUNCH_WIDE_AS(H, L, ACT_, NOA_, HEAD_)                                                                  \
     hipLaunchKernelGGL((rollout_split_kernel<P, H, L, ACT_, NOA_, HEAD_>), dim3((int)((n * L + 255) / 256)), dim3(512), \
-                       0, s, p, a, n, (int)T, pd, params, seed, env_id_base, vec_step0, ctr, tr, 1)
+                       0, s, p, a, n, (int)T, pd, params, seed, env_id_base, vec_step0, ctr, tr, 1, select_margin)
 #define LAUNCH_WIDE(H, L)                                                                     \
     do {                                                                                      \
         if (pd.act == 0 && !pd.cont && pd.na == 2) LAUNCH_WIDE_AS(H, L, 0, 2, 2);             \
