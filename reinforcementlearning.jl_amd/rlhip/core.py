@@ -16,6 +16,7 @@ no episode stages; per vec-step  plan! -> PreAct push -> act! -> PostAct push ->
 Host-side only: counters and callbacks.  Everything touching env state, trajectories or parameters is
 a HIP kernel launched through the C ABI by the objects this loop drives.
 """
+import functools
 import time
 
 import torch
@@ -370,11 +371,7 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
     (plan! -> act! -> push! -> optimise!) as ONE C-ABI call per vec-step (rlhip_dqn_vec_step_f32).  Same kernels,
     same order, same counters as `run`: parameters, trajectory and explorer state end bit-identical
     (tests/test_gpu_run.py).  Hooks see the PostAct stage of every step."""
-    import ctypes as C
-
     from . import _lib
-    from ._lib import call
-    from .ops import ptr, stream_ptr
 
     policy, traj = agent.policy, agent.trajectory
     learner, ex = policy.learner, policy.explorer
@@ -389,15 +386,30 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
         # the fused vec-step steps Adam on the vector its kernels read; a dueling net trains another vector than the one they read
         raise NotImplementedError("fused DQN step: plain Q-networks only; a DuelingApproximator (dueling_params) runs on the "
                                   "per-stage loop, rlhip.run")
+    a = _lib.DqnStepArgs()
+    stop_condition, hook = _fused_dqn_begin(agent, env, stop_condition, hook, a)
+    # the gate is should_update_ itself, on the transitions the step's push leaves
+    return _fused_dqn_steps(agent, env, stop_condition, hook, "rlhip_dqn_vec_step_f32", a, a, learner.should_update_, traces.n_env)
+
+
+def _fused_dqn_begin(agent, env, stop_condition, hook, a):
+    """what both fused DQN loops do once their admission checks have passed: the PreExperiment pushes, the policy's action / Q buffers
+    and the rlhip_dqn_step_args fields that stay fixed over the run -> (stop_condition, hook) with their defaults"""
+    import ctypes as C
+
+    from .ops import ptr
+
+    policy, traces = agent.policy, agent.trajectory.container
+    learner, ex = policy.learner, policy.explorer
+    tn = learner.approximator
+    net = tn.network
     stop_condition = stop_condition or StopAfterNSteps(1)
     hook = hook or EmptyHook()
     hook.push_(PRE_EXPERIMENT_STAGE, agent, env)
     agent.push_(PRE_EXPERIMENT_STAGE, env)
-    dev = env.device
     if policy._actions is None:
-        policy._actions = torch.empty(env.n, dtype=torch.int32, device=dev)
-        policy._q = torch.empty((net.n_out, env.n), dtype=torch.float32, device=dev)
-    a = _lib.DqnStepArgs()
+        policy._actions = torch.empty(env.n, dtype=torch.int32, device=env.device)
+        policy._q = torch.empty((net.n_out, env.n), dtype=torch.float32, device=env.device)
     a.kind, a.env_cfg, a.st, a.n = env.kind, C.addressof(env.cfg), C.addressof(env._st), env.n
     a.env_seed, a.env_id_base = env.seed, env.env_id_base
     a.obs, a.last_obs = ptr(env.state()), ptr(env._last_obs)
@@ -413,18 +425,33 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
     a.sampler_seed, a.rho = learner.seed, tn.rho
     a.workspace, a.grad, a.loss, a.gn = ptr(learner.workspace), ptr(learner.grad), ptr(learner.loss), ptr(net.gn)
     a.actions, a.q = ptr(policy._actions), ptr(policy._q)
-    ctrl = traj.controller
+    return stop_condition, hook
+
+
+def _fused_dqn_steps(agent, env, stop_condition, hook, name, args, a, gate, per_step):
+    """the loop of both fused DQN forms and its epilogue: one call of `name` per vec-step on `args` (passed by reference), whose
+    rlhip_dqn_step_args part `a` receives the per-step fields.  `gate(trajectory, count)` is `do_update`, asked with `per_step` times
+    the number of vec-steps the trajectory holds once the step's push has happened (per_step = n_env: the gate counts transitions);
+    it advances the learner's vec-step counter."""
+    import ctypes as C
+
+    from ._lib import call
+    from .ops import stream_ptr
+
+    traj = agent.trajectory
+    learner, ex = agent.policy.learner, agent.policy.explorer
+    tn = learner.approximator
+    traces, ctrl = traj.container, traj.controller
     s = stream_ptr()
     while True:
         a.eps, a.explorer_step = ex.get_eps(), ex.step
         ex.step += 1
-        # the transition pushed by this call counts towards min_replay_history / the sample-ratio controller
+        # the transition pushed by this call counts towards min_replay_history / the sample-ratio controller / the n-step guard
         ctrl.on_insert_(1)
-        n_after = min(len(traces) + 1, traces.capacity) * traces.n_env
-        a.do_update = int(learner.should_update_(traj, n_after))  # warm-up, update_freq, sample / insert controller
+        a.do_update = int(gate(traj, min(len(traces) + 1, traces.capacity) * per_step))  # warm-up, update_freq, sample / insert controller
         a.draw_ctr = learner.draw_ctr
         a.do_sync = int(a.do_update and (tn.n_optimise + 1) % tn.sync_freq == 0)
-        call("rlhip_dqn_vec_step_f32", C.byref(a), s)
+        call(name, C.byref(args), s)
         if a.do_update:
             learner.draw_ctr += 1
             learner.n_updates += 1
@@ -451,35 +478,19 @@ def _folded_update_gate(learner, trajectory, len_after):
 def _folded_scratch(learner, traces, net):
     """(folded ring, idx, iota, fold workspace or None): the scratch DQNLearner makes with its first folded update -- owned by the
     same NStepBatchSampler / DoubleTargetFold objects, so a later rlhip.run on the agent finds what it would have made itself"""
-    from . import _lib
-    from .trajectory import CircularArraySARTSTraces, DoubleTargetFold
+    from .trajectory import folded_scratch
 
     b, dev = learner.batchsize, traces.state.device
-    owner = learner._nstep
-    if learner.double_dqn:
-        if learner._double is None:
-            learner._double = DoubleTargetFold()
-        if owner is None:
-            owner = learner._double
-    if owner._folded is None or owner._folded.n_env != b or owner._folded.obs_dim != traces.obs_dim:
-        owner._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=dev)
-        owner._iota = torch.empty(b, dtype=torch.int64, device=dev)
+    double = learner._double_fold() if learner.double_dqn else None
+    folded, iota = folded_scratch(learner._nstep if learner._nstep is not None else double, traces, b)
     idx = torch.empty(b, dtype=torch.int64, device=dev)
-    if learner.double_dqn:  # the per-stage Double DQN update leaves the indices its fold took in `_idx`: the draw, or the n-step iota
-        learner._idx = idx if learner._nstep is None else owner._iota
-    ws = None
-    if learner.double_dqn:
-        d = learner._double
-        if learner._nstep is not None and (d._own_iota is None or d._own_iota.numel() != b or d._own_iota.device != dev):
-            d._own_iota = torch.arange(b, dtype=torch.int64, device=dev)  # the in-place fold's index vector of the per-stage loop
-        key = (net.n_in, net.hidden, net.n_out, b, net.layers)
-        if d._ws_key != key:
-            nbytes = int(_lib.lib.rlhip_dqn_double_workspace_bytes(*key))
-            if nbytes < 0:
-                raise ValueError("rlhip_dqn_double_workspace_bytes: bad network / batch description")
-            d._ws, d._ws_key = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), key
-        ws = d._ws
-    return owner._folded, idx, owner._iota, ws
+    if double is None:
+        return folded, idx, iota, None
+    # the per-stage Double DQN update leaves the indices its fold took in `_idx`: the draw, or the n-step iota
+    learner._idx = idx if learner._nstep is None else iota
+    if learner._nstep is not None:
+        double.own_iota(b, dev)  # the in-place fold's index vector of the per-stage loop
+    return folded, idx, iota, double.workspace(net, b, dev)
 
 
 def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
@@ -491,8 +502,7 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
     import ctypes as C
 
     from . import _lib
-    from ._lib import call
-    from .ops import ptr, stream_ptr
+    from .ops import ptr
 
     policy, traj = agent.policy, agent.trajectory
     learner, ex = policy.learner, policy.explorer
@@ -513,31 +523,8 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
                                   "per-stage loop, rlhip.run")
     n_step, double = int(getattr(learner, "n_step", 1)), bool(getattr(learner, "double_dqn", False))
     dueling = getattr(net, "dueling_params", None) is not None
-    stop_condition = stop_condition or StopAfterNSteps(1)
-    hook = hook or EmptyHook()
-    hook.push_(PRE_EXPERIMENT_STAGE, agent, env)
-    agent.push_(PRE_EXPERIMENT_STAGE, env)
-    dev = env.device
-    if policy._actions is None:
-        policy._actions = torch.empty(env.n, dtype=torch.int32, device=dev)
-        policy._q = torch.empty((net.n_out, env.n), dtype=torch.float32, device=dev)
     f = _lib.DqnFoldStepArgs()
-    a = f.base
-    a.kind, a.env_cfg, a.st, a.n = env.kind, C.addressof(env.cfg), C.addressof(env._st), env.n
-    a.env_seed, a.env_id_base = env.seed, env.env_id_base
-    a.obs, a.last_obs = ptr(env.state()), ptr(env._last_obs)
-    a.ring = C.addressof(traces.rb)
-    a.layers, a.h, a.na, a.act = net.layers, net.hidden, net.n_out, net.act
-    a.params, a.target = ptr(net.params), ptr(tn.target)
-    a.packed = ptr(net.packed) if net.layers == 3 else None
-    a.target_packed = ptr(tn.target_packed) if net.layers == 3 else None
-    a.m, a.v, a.beta_pow = ptr(net.m), ptr(net.v), ptr(net.beta_pow)
-    a.lr, a.beta1, a.beta2, a.adam_eps = net.lr, net.beta1, net.beta2, net.eps
-    a.max_grad_norm, a.grad_scale = learner.max_grad_norm, 1.0
-    a.explorer_seed, a.batch, a.gamma, a.huber_delta = ex.seed, learner.batchsize, learner.gamma, learner.delta
-    a.sampler_seed, a.rho = learner.seed, tn.rho
-    a.workspace, a.grad, a.loss, a.gn = ptr(learner.workspace), ptr(learner.grad), ptr(learner.loss), ptr(net.gn)
-    a.actions, a.q = ptr(policy._actions), ptr(policy._q)
+    stop_condition, hook = _fused_dqn_begin(agent, env, stop_condition, hook, f.base)
     f.n_step, f.double_dqn, f.td = n_step, int(double), ptr(learner.td)
     if n_step > 1 or double:
         folded, idx, iota, ws = _folded_scratch(learner, traces, net)
@@ -545,28 +532,8 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
         f.fold_workspace = ptr(ws) if ws is not None else None
     if dueling:
         f.dueling_params, f.target_dueling, f.grad_dueling = ptr(net.dueling_params), ptr(tn.target_dueling), ptr(net._grad.t)
-    ctrl = traj.controller
-    s = stream_ptr()
-    while True:
-        a.eps, a.explorer_step = ex.get_eps(), ex.step
-        ex.step += 1
-        # the transition pushed by this call counts towards min_replay_history / the sample-ratio controller / the n-step guard
-        ctrl.on_insert_(1)
-        a.do_update = int(_folded_update_gate(learner, traj, min(len(traces) + 1, traces.capacity)))
-        a.draw_ctr = learner.draw_ctr
-        a.do_sync = int(a.do_update and (tn.n_optimise + 1) % tn.sync_freq == 0)
-        call("rlhip_dqn_vec_step_fold_f32", C.byref(f), s)
-        if a.do_update:
-            learner.draw_ctr += 1
-            learner.n_updates += 1
-            tn.n_optimise = 0 if a.do_sync else tn.n_optimise + 1
-        hook.push_(POST_ACT_STAGE, agent, env)
-        if stop_condition.check_(agent, env):
-            break
-    env._obs_valid = True
-    agent.push_(POST_EXPERIMENT_STAGE, env)
-    hook.push_(POST_EXPERIMENT_STAGE, agent, env)
-    return hook
+    return _fused_dqn_steps(agent, env, stop_condition, hook, "rlhip_dqn_vec_step_fold_f32", f, f.base,
+                            functools.partial(_folded_update_gate, learner), 1)
 
 
 def run_fused_ppo(policy, env, n_updates, hook=None):

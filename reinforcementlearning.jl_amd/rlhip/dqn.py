@@ -328,7 +328,13 @@ class DQNLearner:
     (|td| + per_eps)^per_alpha is written back, and -- round 4 -- the loss carries the importance-sampling weights
     of PrioritizedDQN when `per_beta > 0`: w = 1 ./ ((priority .+ 1f-10) .^ beta), w ./= maximum(w),
     loss = mean(w .* huber(td)) (`per_beta` may be a callable n_updates -> beta for the usual annealing towards 1;
-    per_beta = 0, the default, is the proportional-sampling variant without weights)."""
+    per_beta = 0, the default, is the proportional-sampling variant without weights).
+
+    Every form -- 1-step or n-step, uniform or prioritized, plain or Double DQN targets -- is the same pipeline behind optimise_'s
+    gate (`_update_`), each stage defined once: `_draw_` (the batch as a (ring, idx) pair with its discount), `_is_weights_`
+    (prioritized traces, beta > 0), the DoubleTargetFold (`double_dqn`), `_gradient_` (the one choice of the gradient entry, by
+    layers and weights), the priority write-back under the drawn keys, `_exchange_and_apply_`.  A stage a form does not need is
+    skipped, and the plain learner keeps its shortest form: no draw of its own, the gradient launch samples."""
 
     def __init__(self, approximator, batchsize=32, gamma=0.99, huber_delta=1.0, min_replay_history=100,
                  update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
@@ -341,7 +347,7 @@ class DQNLearner:
         max Qt(s').  Every per-stage update form folds its sampled batch first (DoubleTargetFold: the finished target y in the
         reward field, terminal = 1) and runs the same gradient kernels on the folded ring; the fused vec-step stays plain DQN."""
         self.double_dqn = bool(double_dqn)
-        self._double = None  # the DoubleTargetFold, made by the first folded update (a checkpoint carries the flag, not the scratch)
+        self._double = None  # the DoubleTargetFold: see _double_fold
         self.n_step = int(n_step)
         self._nstep = None
         if self.n_step > 1:
@@ -392,149 +398,85 @@ class DQNLearner:
                              f"these traces mask windows of {getattr(traces, 'n_step', 1)}")
         if not self.should_update_(trajectory):
             return False
-        net = self.approximator.network
-        if self._nstep is not None and prioritized:
-            return self._optimise_per_nstep_(traces)
-        if self.double_dqn:
-            return self._optimise_double_(traces, prioritized)
-        if self._nstep is not None:
-            folded, iota = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
-            if net.layers == 3:
-                dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, self.approximator.target,
-                          self.approximator.target_packed, self.batchsize, self._nstep.gamma_n, self.delta, self.seed, self.draw_ctr,
-                          iota, self.workspace, self.grad, self.loss, self.td)
-            else:
-                call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params),
-                     ptr(self.approximator.target), self.batchsize, ptr(iota), self._nstep.gamma_n, self.delta, ptr(self.workspace),
-                     ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
-            return self._exchange_and_apply_()
-        beta = 0.0
-        if prioritized:
-            beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
-        if net.layers == 3:
-            idx = None
-            if prioritized:  # prioritized BatchSampler: keys + priorities from the device sum-tree
-                idx, self._key, self._prio = traces.sample_prioritized(self.batchsize, self.seed, self.draw_ctr)
-            if prioritized and beta > 0.0:
-                call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
-                call("rlhip_dqn3_grad_w_f32", C.byref(traces.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
-                     ptr(self.approximator.target), ptr(self.approximator.target_packed), self.batchsize, ptr(idx),
-                     ptr(self.is_weights), self.gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
-                     ptr(self.td), stream_ptr())
-            else:
-                dqn3_grad(traces, net.hidden, net.n_out, net.act, net.params, net.packed, self.approximator.target,
-                          self.approximator.target_packed, self.batchsize, self.gamma, self.delta, self.seed,
-                          self.draw_ctr, idx, self.workspace, self.grad, self.loss, self.td)
-            if prioritized:  # trajectory[:priority, keys] = (|td| + eps)^alpha  (PrioritizedDQN write-back)
-                call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha,
-                     ptr(self.td), stream_ptr())
-                traces.set_priority_(self._key, self.td)
-        elif prioritized:
-            idx, self._key, self._prio = traces.sample_prioritized(self.batchsize, self.seed, self.draw_ctr)
-            if beta > 0.0:
-                call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
-                call("rlhip_dqn_grad_idx_w_f32", C.byref(traces.rb), net.hidden, net.n_out, net.act, ptr(net.params),
-                     ptr(self.approximator.target), self.batchsize, ptr(idx), ptr(self.is_weights), self.gamma, self.delta,
-                     ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
-            else:
-                call("rlhip_dqn_grad_idx_f32", C.byref(traces.rb), net.hidden, net.n_out, net.act, ptr(net.params),
-                     ptr(self.approximator.target), self.batchsize, ptr(idx), self.gamma, self.delta, ptr(self.workspace),
-                     ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
-            call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td),
-                 stream_ptr())
-            traces.set_priority_(self._key, self.td)
-        else:
-            dqn_grad(traces, net.hidden, net.n_out, net.act, net.params, self.approximator.target, self.batchsize,
-                     self.gamma, self.delta, self.seed, self.draw_ctr, self.workspace, self.grad, self.loss)
-        return self._exchange_and_apply_()
+        return self._update_(traces, prioritized)
 
-    def _optimise_double_(self, traces, prioritized):
-        """optimise! with Double DQN targets: the batch every form samples (same draws, same keys) is folded, then the `_idx` /
-        `_idx_w` / dqn3 gradient entry runs on the folded ring with its iota.  td = |Q(s, a) - y| goes back under the ORIGINAL keys."""
-        tn = self.approximator
-        net = tn.network
-        if self._double is None:  # also the learner built without the flag that loaded a double_dqn = True checkpoint
-            from .trajectory import DoubleTargetFold
-
-            self._double = DoubleTargetFold()
-        gamma, in_place, weights = self.gamma, False, None
-        if self._nstep is not None:  # (uniform replay: prioritized n-step batches take _optimise_per_nstep_)
-            src, idx = self._nstep.fold(traces, self._nstep.sample_indices(traces, self.draw_ctr))
-            gamma, in_place = self._nstep.gamma_n, True  # the n-step ring is rewritten in place, gamma^n as the discount
-        elif prioritized:
-            src = traces
-            idx, self._key, self._prio = traces.sample_prioritized(self.batchsize, self.seed, self.draw_ctr)
-            beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
-            if beta > 0.0:
-                call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
-                weights = self.is_weights
-        else:  # the draw rlhip_dqn_grad_f32 evaluates inline: the flag does not change which transitions are sampled
-            src, idx = traces, traces.sample_indices(self.batchsize, self.seed, self.draw_ctr)
-        self._idx = idx
-        folded, iota = self._double.fold(src, None if in_place else idx, net, tn.target, tn.target_packed, gamma, in_place)
-        if net.layers == 3:
-            if weights is not None:
-                call("rlhip_dqn3_grad_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
-                     ptr(tn.target), ptr(tn.target_packed), self.batchsize, ptr(iota), ptr(weights), gamma, self.delta,
-                     ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
-            else:
-                dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, tn.target, tn.target_packed,
-                          self.batchsize, gamma, self.delta, self.seed, self.draw_ctr, iota, self.workspace, self.grad, self.loss,
-                          self.td)
-        elif weights is not None:
-            call("rlhip_dqn_grad_idx_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
-                 self.batchsize, ptr(iota), ptr(weights), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
-                 ptr(self.td), stream_ptr())
-        else:
-            call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
-                 self.batchsize, ptr(iota), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td),
-                 stream_ptr())
-        if prioritized:  # trajectory[:priority, keys] = (|td| + eps)^alpha  (PrioritizedDQN write-back)
+    def _update_(self, traces, prioritized):
+        """one update behind the gate, the same stages for every form: draw, importance-sampling weights, Double DQN fold, gradient,
+        priority write-back, exchange and apply"""
+        ring, idx, gamma, in_place = self._draw_(traces, prioritized)
+        weights = self._is_weights_() if prioritized else None
+        if self.double_dqn:  # the finished target y into the reward field; an n-step ring is rewritten in place, gamma^n as the discount
+            tn = self.approximator
+            ring, idx = self._double_fold().fold(ring, None if in_place else idx, tn.network, tn.target, tn.target_packed, gamma, in_place)
+        self._gradient_(ring, idx, gamma, weights)
+        if prioritized:  # trajectory[:priority, keys] = (|td| + eps)^alpha under the ORIGINAL keys, in this call: before any further push
             call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
             traces.set_priority_(self._key, self.td)
         return self._exchange_and_apply_()
 
-    def _optimise_per_nstep_(self, traces):
-        """optimise! with n-step targets on prioritized traces (CircularPrioritizedTraces(n_step = n): window starts drawn from the
-        masked tree).  Draw + window fold in one launch, importance-sampling weights from the drawn priorities, the Double DQN fold in
-        place on the folded ring with gamma^n, the unchanged gradient entry on (folded, iota) with gamma^n, and (|td| + eps)^alpha
-        written back under the ORIGINAL keys -- in this call, before any further push, so a masked leaf is never written."""
+    def _draw_(self, traces, prioritized):
+        """-> (ring, idx, discount, whether `ring` is a folded batch of this learner's that a Double DQN fold may rewrite in place).
+        Prioritized draws leave their keys and priorities in `_key` / `_prio`; `_idx` is set by every Double DQN form (the indices its
+        fold takes) and by the prioritized n-step form (the drawn window starts)."""
+        smp = self._nstep
+        if smp is not None and prioritized:  # window starts from the masked tree, draw + window fold in one launch
+            ring, idx, self._idx, self._key, self._prio = smp.sample_fold_prioritized(traces, self.draw_ctr)
+            return ring, idx, smp.gamma_n, True
+        ring, gamma, in_place = traces, self.gamma, False
+        if smp is not None:
+            ring, idx = smp.fold(traces, smp.sample_indices(traces, self.draw_ctr))
+            gamma, in_place = smp.gamma_n, True
+        elif prioritized:  # prioritized BatchSampler: keys + priorities from the device sum-tree
+            idx, self._key, self._prio = traces.sample_prioritized(self.batchsize, self.seed, self.draw_ctr)
+        elif self.double_dqn:  # the draw the plain gradient launch evaluates inline: the flag does not change which transitions are sampled
+            idx = traces.sample_indices(self.batchsize, self.seed, self.draw_ctr)
+        else:
+            idx = None  # the plain learner: the draw happens inside the gradient launch
+        if self.double_dqn:
+            self._idx = idx
+        return ring, idx, gamma, in_place
+
+    def _is_weights_(self):
+        """importance-sampling weights of the drawn priorities -> `is_weights`, or None while beta = 0"""
+        beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
+        if not beta > 0.0:
+            return None
+        call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
+        return self.is_weights
+
+    def _double_fold(self):
+        """the learner's DoubleTargetFold, made on first use (a checkpoint carries the flag, not the scratch: a learner built without
+        the flag that loaded a double_dqn = True checkpoint makes it here too)"""
+        if self._double is None:
+            from .trajectory import DoubleTargetFold
+
+            self._double = DoubleTargetFold()
+        return self._double
+
+    def _gradient_(self, ring, idx, gamma, weights):
+        """the gradient entry for (layers, weights or not) on `ring` at `idx` -> grad, loss, td.  idx = None is the plain learner, which
+        draws inside the launch: two layers take the entry without indices (and without td), three a NULL index pointer."""
         tn = self.approximator
         net = tn.network
-        smp = self._nstep
-        folded, iota, idx, self._key, self._prio = smp.sample_fold_prioritized(traces, self.draw_ctr)
-        self._idx = idx
-        gamma, weights = smp.gamma_n, None
-        beta = float(self.per_beta(self.n_updates)) if callable(self.per_beta) else float(self.per_beta)
-        if beta > 0.0:
-            call("rlhip_per_is_weights_f32", ptr(self._prio), self.batchsize, beta, ptr(self.is_weights), stream_ptr())
-            weights = self.is_weights
-        if self.double_dqn:
-            if self._double is None:
-                from .trajectory import DoubleTargetFold
-
-                self._double = DoubleTargetFold()
-            folded, iota = self._double.fold(folded, None, net, tn.target, tn.target_packed, gamma, in_place=True)
         if net.layers == 3:
             if weights is not None:
-                call("rlhip_dqn3_grad_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
-                     ptr(tn.target), ptr(tn.target_packed), self.batchsize, ptr(iota), ptr(weights), gamma, self.delta,
+                call("rlhip_dqn3_grad_w_f32", C.byref(ring.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(net.packed),
+                     ptr(tn.target), ptr(tn.target_packed), self.batchsize, ptr(idx), ptr(weights), gamma, self.delta,
                      ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td), stream_ptr())
             else:
-                dqn3_grad(folded, net.hidden, net.n_out, net.act, net.params, net.packed, tn.target, tn.target_packed,
-                          self.batchsize, gamma, self.delta, self.seed, self.draw_ctr, iota, self.workspace, self.grad, self.loss,
-                          self.td)
+                dqn3_grad(ring, net.hidden, net.n_out, net.act, net.params, net.packed, tn.target, tn.target_packed, self.batchsize,
+                          gamma, self.delta, self.seed, self.draw_ctr, idx, self.workspace, self.grad, self.loss, self.td)
         elif weights is not None:
-            call("rlhip_dqn_grad_idx_w_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
-                 self.batchsize, ptr(iota), ptr(weights), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
+            call("rlhip_dqn_grad_idx_w_f32", C.byref(ring.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(idx), ptr(weights), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss),
                  ptr(self.td), stream_ptr())
-        else:
-            call("rlhip_dqn_grad_idx_f32", C.byref(folded.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
-                 self.batchsize, ptr(iota), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td),
+        elif idx is not None:
+            call("rlhip_dqn_grad_idx_f32", C.byref(ring.rb), net.hidden, net.n_out, net.act, ptr(net.params), ptr(tn.target),
+                 self.batchsize, ptr(idx), gamma, self.delta, ptr(self.workspace), ptr(self.grad), ptr(self.loss), ptr(self.td),
                  stream_ptr())
-        call("rlhip_per_priority_f32", ptr(self.td), self.batchsize, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
-        traces.set_priority_(self._key, self.td)
-        return self._exchange_and_apply_()
+        else:
+            dqn_grad(ring, net.hidden, net.n_out, net.act, net.params, tn.target, self.batchsize, gamma, self.delta, self.seed,
+                     self.draw_ctr, self.workspace, self.grad, self.loss)
 
     def _exchange_and_apply_(self):
         """the tail of every update form (1-step, n-step, prioritized): draw counter, gradient all-reduce over the process group,

@@ -269,6 +269,16 @@ class BatchSampler:
         return dict(state=s, action=a + 1, reward=r, terminal=t.view(torch.bool), next_state=sn, **extra)
 
 
+def folded_scratch(owner, traces, b):
+    """-> (`owner._folded`, `owner._iota`): the record ring of capacity 1 x `b` envs that holds a folded batch of `traces` and its
+    index vector, made anew when the batch size or the observation width changes"""
+    if owner._folded is None or owner._folded.n_env != b or owner._folded.obs_dim != traces.obs_dim:
+        device = traces.state.device  # (a view of the records: only looked up when something is allocated)
+        owner._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=device)
+        owner._iota = torch.empty(b, dtype=torch.int64, device=device)
+    return owner._folded, owner._iota
+
+
 class NStepBatchSampler:
     """NStepBatchSampler(n, gamma, batchsize; rng) of RLTrajectories 0.4 (un-vendored; oracle/rlo_buffer.c restates it): start
     indices with n transitions ahead of them, each window folded on the device into ONE transition
@@ -294,12 +304,6 @@ class NStepBatchSampler:
                              "construct CircularPrioritizedTraces(..., n_step = n)")
         return True
 
-    def _folded_ring(self, traces, b):
-        if self._folded is None or self._folded.n_env != b or self._folded.obs_dim != traces.obs_dim:
-            self._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=traces.state.device)
-            self._iota = torch.empty(b, dtype=torch.int64, device=traces.state.device)
-        return self._folded, self._iota
-
     def sample_indices(self, traces, draw_ctr=None):
         """window starts: uniform over 1:(length - n + 1) per env; over CircularPrioritizedTraces(n_step = n) in proportion to the
         masked priorities (the shipped prioritized draw), with `.key` / `.priority` of the draw kept on the sampler"""
@@ -320,7 +324,7 @@ class NStepBatchSampler:
             raise TypeError("sample_fold_prioritized takes CircularPrioritizedTraces(n_step = n)")
         ctr = self.draw_ctr if draw_ctr is None else draw_ctr
         b, dev = self.batchsize, traces.state.device
-        folded, iota = self._folded_ring(traces, b)
+        folded, iota = folded_scratch(self, traces, b)
         if self._draw is None or self._draw[0].numel() != b or self._draw[0].device != dev:
             self._draw = (torch.empty(b, dtype=torch.int64, device=dev), torch.empty(b, dtype=torch.int64, device=dev),
                           torch.empty(b, dtype=torch.float32, device=dev))
@@ -339,7 +343,7 @@ class NStepBatchSampler:
             idx = self.sample_indices(traces)
             self.draw_ctr += 1
         b = idx.numel()
-        folded, iota = self._folded_ring(traces, b)
+        folded, iota = folded_scratch(self, traces, b)
         call("rlhip_ring_fold_nstep", C.byref(traces.rb), ptr(idx), b, self.n, self.gamma, C.byref(folded.rb), ptr(iota), stream_ptr())
         return folded, iota
 
@@ -364,29 +368,34 @@ class DoubleTargetFold:
         self._folded = self._iota = self._own_iota = self._ws = None
         self._ws_key = None
 
+    def own_iota(self, b, device):
+        """0, 1, .., b - 1: the index vector of the in-place fold"""
+        if self._own_iota is None or self._own_iota.numel() != b or self._own_iota.device != device:
+            self._own_iota = torch.arange(b, dtype=torch.int64, device=device)
+        return self._own_iota
+
+    def workspace(self, network, b, device):
+        """the fold kernels' workspace for `network` at batch `b` (None where they need none), sized when either changes"""
+        key = (network.n_in, network.hidden, network.n_out, b, network.layers)
+        if self._ws_key != key:
+            nbytes = int(_lib.lib.rlhip_dqn_double_workspace_bytes(*key))
+            if nbytes < 0:
+                raise ValueError("rlhip_dqn_double_workspace_bytes: bad network / batch description")
+            self._ws, self._ws_key = (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), key
+        return self._ws
+
     def fold(self, traces, idx, network, target, target_packed, gamma_eff, in_place=False):
         """-> (folded traces, iota); `network` is a HipApproximator (2 or 3 layers), `target` / `target_packed` its target copy"""
         if in_place:
             if idx is not None:
                 raise ValueError("the in-place fold walks the ring's own records 0 .. n_env - 1: pass idx = None")
             b, dev = traces.n_env, traces.state.device
-            if self._own_iota is None or self._own_iota.numel() != b or self._own_iota.device != dev:
-                self._own_iota = torch.arange(b, dtype=torch.int64, device=dev)
-            folded, iota = traces, self._own_iota
-            idx = iota
+            folded = traces
+            idx = iota = self.own_iota(b, dev)
         else:
             b, dev = idx.numel(), idx.device
-            if self._folded is None or self._folded.n_env != b or self._folded.obs_dim != traces.obs_dim:
-                self._folded = CircularArraySARTSTraces(capacity=1, n_env=b, obs_dim=traces.obs_dim, device=dev)
-                self._iota = torch.empty(b, dtype=torch.int64, device=dev)
-            folded, iota = self._folded, self._iota
-        key = (network.n_in, network.hidden, network.n_out, b, network.layers)
-        if self._ws_key != key:
-            nbytes = int(_lib.lib.rlhip_dqn_double_workspace_bytes(*key))
-            if nbytes < 0:
-                raise ValueError("rlhip_dqn_double_workspace_bytes: bad network / batch description")
-            self._ws, self._ws_key = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), key
-        ws = ptr(self._ws) if self._ws is not None else None
+            folded, iota = folded_scratch(self, traces, b)  # allocated on the traces' device: the one `idx` was drawn on
+        ws = ptr(self.workspace(network, b, dev))
         if network.layers == 3:
             call("rlhip_dqn3_fold_double_f32", C.byref(traces.rb), network.hidden, network.n_out, network.act, ptr(network.params),
                  ptr(network.packed), ptr(target), ptr(target_packed), ptr(idx), b, gamma_eff, C.byref(folded.rb), ptr(iota), ws,

@@ -210,7 +210,7 @@ def _gate_learner(n_step, update_freq, min_replay_history):
             self.update_freq, self.min_replay_history = update_freq, min_replay_history
             self.approximator = NS(network=None)
 
-        def _optimise_double_(self, traces, prioritized):
+        def _update_(self, traces, prioritized):
             assert len(traces) >= self.n_step, "an update without one full window"
             self.draw_ctr += 1
             self.n_updates += 1
