@@ -678,6 +678,43 @@ struct rlhip_dqn_fold_step_args_s { /* (a tagged struct with its typedef below: 
 typedef struct rlhip_dqn_fold_step_args_s rlhip_dqn_fold_step_args;
 int32_t rlhip_dqn_vec_step_fold_f32(rlhip_dqn_fold_step_args* args, rlhip_stream_t stream);
 
+/* ------------------------------ the same vec-step for a learner over prioritized replay -- */
+/* One trip round the body of `_run` (RLCore/src/core/run.jl:52-70), as rlhip_dqn_vec_step_fold_f32, for a learner whose trajectory is
+ * `CircularPrioritizedTraces` of RLTrajectories 0.4 sampled by the prioritized `BatchSampler` (n_step == 1) or by `NStepBatchSampler`
+ * over the masked tree (n_step > 1) -- the removed Zoo's PrioritizedDQN, with any of Double DQN targets, a DuelingNetwork and
+ * importance-sampling weights (un-vendored: PARITY UNPINNED like the entries it composes).  It enqueues what the per-stage learner
+ * enqueues, in the same order with the same arguments:
+ *     plan! + act! + push!                as rlhip_dqn_vec_step_f32
+ *     rlhip_ring_push_priority (n_step == 1) / rlhip_ring_push_priority_nstep            -- return here when !do_update
+ *     rlhip_ring_sample_prioritized(ring, tree, batch, sampler_seed, draw_ctr, idx, key, prio) (n_step == 1) /
+ *         rlhip_per_sample_fold_nstep_f32(..., idx, key, prio, folded, iota)
+ *     rlhip_per_is_weights_f32(prio, batch, per_beta, is_weights)                         when per_beta > 0
+ *     rlhip_dqn_fold_double_f32 / rlhip_dqn3_fold_double_f32                              when double_dqn: from the trajectory with idx
+ *         into (folded, iota), or in place on (folded, iota) when n_step > 1
+ *     the gradient entry point: on (folded, iota) with rlhip_gamma_pow(gamma, n_step) when n_step > 1 or double_dqn, on (ring, idx)
+ *         with gamma otherwise; rlhip_dqn_grad_idx_w_f32 / rlhip_dqn3_grad_w_f32 with the weights, rlhip_dqn_grad_idx_f32 /
+ *         rlhip_dqn3_grad_f32 without; td into fold.td
+ *     rlhip_per_writeback_f32(tree, capacity * n_env, key, fold.td, batch, per_eps, per_alpha, priority_out)
+ *     the tail of rlhip_dqn_vec_step_fold_f32 (clip + Adam [+ pack], on do_sync Polyak [+ pack]; the dueling vectors for a dueling net)
+ * so results -- parameters, optimiser state, trajectory, tree -- are bit-identical to the per-stage protocol.  Every argument is
+ * checked before the first launch (everything rlhip_dqn_vec_step_fold_f32 checks; a record ring; the network shapes of the gradient
+ * entry points; tree non-NULL; default_priority > 0; per_eps, per_alpha, per_beta >= 0; n_step <= capacity; with do_update idx, key,
+ * prio, fold.td and priority_out present, is_weights when per_beta > 0, priority_out not overlapping fold.td): a refused call moves
+ * no counter.  (Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.) */
+struct rlhip_dqn_per_step_args_s {
+    rlhip_dqn_fold_step_args fold; /* every field as documented there; fold.td = TD errors out, f32[batch], required when do_update */
+    float* tree;                   /* the traces' sum-tree (rlhip_sumtree_nodes(capacity * n_env) floats) */
+    float default_priority;        /* > 0 */
+    float per_eps, per_alpha;      /* write-back value (|td| + eps)^alpha */
+    float per_beta;                /* this update's beta (the host evaluates a schedule); 0: no importance-sampling weights */
+    int64_t* key;                  /* i64[batch]: the drawn physical keys */
+    float* prio;                   /* f32[batch]: their priorities */
+    float* is_weights;             /* f32[batch]; required when per_beta > 0 */
+    float* priority_out;           /* f32[batch]: the written-back priorities; must not overlap fold.td */
+};
+typedef struct rlhip_dqn_per_step_args_s rlhip_dqn_per_step_args;
+int32_t rlhip_dqn_vec_step_per_f32(rlhip_dqn_per_step_args* args, rlhip_stream_t stream);
+
 /* ------------------------------------------------------ 3-layer Q-network on the MFMA -- */
 /* Chain(Dense(ns, 128, act), Dense(128, 128, act), Dense(128, na)) -- the blog's DQN model
  * (docs/homepage/blog/a_practical_introduction_to_RL.jl/index.html:15126-15128), forward(learner, x) =
@@ -758,6 +795,17 @@ int32_t rlhip_sumtree_sample(const float* tree, int64_t n_leaves, int64_t batch,
 /* PrioritizedDQN priority write-back value: out = (|td| + eps)^alpha (power in Float64, rounded once) */
 int32_t rlhip_per_priority_f32(const float* td, int64_t n, float eps, float alpha, float* out,
                                rlhip_stream_t stream);
+/* The two lines above and below as ONE launch -- PrioritizedDQN's `trajectory[:priority, keys] = (|td| .+ eps) .^ alpha` over
+ * `CircularPrioritizedTraces` (RLTrajectories 0.4; un-vendored, PARITY UNPINNED): prio_out[i] = (|td[i]| + eps)^alpha for every i
+ * (the power in Float64, rounded once; alpha == 1 takes no power), stored by item number whatever key[i] is, and tree[key] = prio_out
+ * with the semantics of rlhip_sumtree_update (the last duplicate wins, out-of-range keys are never written, every parent is
+ * left + right of its stored children, tree[0] is left at 0).  The tree (every node) and prio_out are byte for byte those of
+ * rlhip_per_priority_f32(td -> prio_out) followed by rlhip_sumtree_update(tree, key, prio_out): the same kernels with the power of
+ * td[item] as their value source, the same dispatch (one wave up to 64 keys, one workgroup up to 2^13 leaves, 32 / 128 / 256
+ * workgroups above).  n == 0 returns without a launch.  prio_out is required and must not overlap td (workgroups read td while
+ * others write prio_out): RLHIP_EINVAL before any launch.  Checks on eps, alpha, n and NULL pointers as the two entries. */
+int32_t rlhip_per_writeback_f32(float* tree, int64_t n_leaves, const int64_t* key, const float* td, int64_t n, float eps,
+                                float alpha, float* prio_out, rlhip_stream_t stream);
 /* importance-sampling weights of the sampled batch (PrioritizedDQN, removed Zoo; Schaul et al. 2016):
  *   w = 1 ./ ((priorities .+ 1f-10) .^ beta);  w ./= maximum(w)      (powers in Float64, rounded once)
  * -- the N and total-priority factors of (N P(i))^-beta cancel in the normalisation.  PARITY UNPINNED. */

@@ -1,6 +1,6 @@
 // sumtree_device.h -- the one-wavefront priority write-back (<= 64 keys) as a device function, shared by its own launch
-// (sumtree.hip: rlhip_sumtree_update) and by the prologue of the fused "update -> draw -> gather" launch (ring.hip, round 6); and the
-// descent of one prioritized draw.
+// (sumtree.hip: rlhip_sumtree_update), by the prologue of the fused "update -> draw -> gather" launch (ring.hip, round 6) and by the
+// fused power + write-back (per_writeback.hip); the value sources of a write-back; and the descent of one prioritized draw.
 #pragma once
 #include "common.h"
 
@@ -8,6 +8,31 @@ namespace rlhip {
 
 constexpr int SMALL_UPDATE_MAX = 64;
 constexpr int SMALL_MAXL = 32;  // levels (n_leaves < 2^31)
+
+// PrioritizedDQN write-back value p = (|td| + eps)^alpha: the power in Float64, rounded once (per_priority_kernel's line, and the
+// power source below: one definition, the same bits)
+__device__ __forceinline__ float per_priority_value(float td, float eps, float alpha) {
+    float x = fabsf(td) + eps;
+    return (alpha == 1.0f) ? x : (float)pow((double)x, (double)alpha);
+}
+
+// Where a write-back takes the value of item i from.  PrioLoad: the caller's priority array (rlhip_sumtree_update).  PrioPower: the
+// power of td[i] (rlhip_per_writeback_f32) -- a pure function of td[i], so whichever lane needs item i's value evaluates it again;
+// `publish` leaves it in out[i], by item number, whatever the item's key is.
+struct PrioLoad {
+    static constexpr bool PUBLISHES = false;
+    const float* __restrict__ prio;
+    __device__ __forceinline__ float operator()(int64_t i) const { return prio[i]; }
+    __device__ __forceinline__ void publish(int64_t, float) const {}
+};
+struct PrioPower {
+    static constexpr bool PUBLISHES = true;
+    const float* __restrict__ td;
+    float eps, alpha;
+    float* __restrict__ out;
+    __device__ __forceinline__ float operator()(int64_t i) const { return per_priority_value(td[i], eps, alpha); }
+    __device__ __forceinline__ void publish(int64_t i, float v) const { out[i] = v; }
+};
 
 // LDS of one call: 64 keys + 64 values + SMALL_MAXL x 64 siblings
 struct SmallUpdateLds {
@@ -39,14 +64,15 @@ __device__ __forceinline__ void tree_store(float* p, float v) {
 
 // Called by ALL 64 lanes of ONE wavefront (uniform control flow); the wave's LDS accesses execute in order, so the exchanges through
 // `sh` need no workgroup barrier (the caller may be one wave of a larger workgroup).  Steps: see sumtree.hip.
-template <bool COHERENT>
+template <bool COHERENT, class Src>
 __device__ __forceinline__ void sumtree_update_small_wave(float* tree, int64_t P, int logP, int64_t n_leaves,
-                                                          const int64_t* __restrict__ leaf, const float* __restrict__ prio, int n,
+                                                          const int64_t* __restrict__ leaf, const Src src, int n,
                                                           SmallUpdateLds& sh) {
     const int lane = (int)threadIdx.x & 63;
     // ---- 1. load; composite sort key = leaf * 64 + item number (invalid / out-of-range keys sort last) ----
     int64_t k = lane < n ? leaf[lane] : -1;
-    float pv = lane < n ? prio[lane] : 0.0f;
+    float pv = lane < n ? src(lane) : 0.0f;
+    if (lane < n) src.publish(lane, pv);
     const bool ok = k >= 0 && k < n_leaves;
     uint64_t ck = ok ? ((uint64_t)k << 6) | (uint64_t)lane : ~0ull;
     // ---- 2. bitonic sort over the 64 lanes (ascending) ----
@@ -129,6 +155,13 @@ __device__ __forceinline__ void sumtree_update_small_wave(float* tree, int64_t P
             }
         }
     }
+}
+
+template <bool COHERENT>
+__device__ __forceinline__ void sumtree_update_small_wave(float* tree, int64_t P, int logP, int64_t n_leaves,
+                                                          const int64_t* __restrict__ leaf, const float* __restrict__ prio, int n,
+                                                          SmallUpdateLds& sh) {
+    sumtree_update_small_wave<COHERENT>(tree, P, logP, n_leaves, leaf, PrioLoad{prio}, n, sh);
 }
 
 }  // namespace rlhip

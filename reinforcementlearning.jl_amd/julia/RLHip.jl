@@ -179,6 +179,21 @@ mutable struct DqnFoldStepArgs   # rlhip_dqn_fold_step_args: `base` (rlhip_dqn_s
     fold_workspace::Ptr{Cvoid}; dueling_params::Ptr{Cvoid}; target_dueling::Ptr{Cvoid}; grad_dueling::Ptr{Cvoid}
     DqnFoldStepArgs() = new()
 end
+mutable struct DqnPerStepArgs   # rlhip_dqn_per_step_args: `fold` (rlhip_dqn_fold_step_args) laid out in place, then the prioritized fields
+    kind::Int32; env_cfg::Ptr{Cvoid}; st::Ptr{Cvoid}; n::Int64; env_seed::UInt64; env_id_base::UInt32
+    obs::Ptr{Cvoid}; last_obs::Ptr{Cvoid}; ring::Ptr{Cvoid}; layers::Int32; h::Int64; na::Int64; act::Int32
+    params::Ptr{Cvoid}; packed::Ptr{Cvoid}; target::Ptr{Cvoid}; target_packed::Ptr{Cvoid}
+    m::Ptr{Cvoid}; v::Ptr{Cvoid}; beta_pow::Ptr{Cvoid}
+    lr::Float32; beta1::Float32; beta2::Float32; adam_eps::Float32; max_grad_norm::Float32; grad_scale::Float32
+    eps::Float64; explorer_seed::UInt64; explorer_step::UInt32; batch::Int64; gamma::Float32; huber_delta::Float32
+    sampler_seed::UInt64; draw_ctr::UInt32; do_update::Int32; do_sync::Int32; rho::Float32
+    workspace::Ptr{Cvoid}; grad::Ptr{Cvoid}; loss::Ptr{Cvoid}; gn::Ptr{Cvoid}; actions::Ptr{Cvoid}; q::Ptr{Cvoid}
+    n_step::Int32; double_dqn::Int32; folded::Ptr{Cvoid}; idx::Ptr{Cvoid}; iota::Ptr{Cvoid}; td::Ptr{Cvoid}
+    fold_workspace::Ptr{Cvoid}; dueling_params::Ptr{Cvoid}; target_dueling::Ptr{Cvoid}; grad_dueling::Ptr{Cvoid}
+    tree::Ptr{Cvoid}; default_priority::Float32; per_eps::Float32; per_alpha::Float32; per_beta::Float32
+    key::Ptr{Cvoid}; prio::Ptr{Cvoid}; is_weights::Ptr{Cvoid}; priority_out::Ptr{Cvoid}
+    DqnPerStepArgs() = new()
+end
 struct CommDesc         # rlhip_comm_desc
     rank::Int32; world::Int32; device::Int32; p2p_active::Int32; rccl_active::Int32
     seq::UInt32; cap::Int64; timeout_polls::Int64; status::Ptr{Cvoid}
@@ -1146,6 +1161,15 @@ dqn3_grad_weighted!(t::HipTrajectory, h, na, act, params::DevBuf{Float32}, packe
                Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
               t.rb, h, na, act, params.ptr, packed.ptr, target.ptr, tpacked.ptr, batch, idx.ptr, w.ptr, γ, δ, workspace.ptr, grad.ptr,
               loss.ptr, td.ptr, stream()))
+"the two calls around this line as ONE launch: out = (|td| + eps)^alpha, then trajectory[:priority, keys] = out (`out` must not overlap `td`)"
+per_writeback!(tree::DevBuf{Float32}, n_leaves, key::DevBuf{Int64}, td::DevBuf{Float32}, n, eps::Float32, alpha::Float32,
+               out::DevBuf{Float32}) =
+    chk(ccall((:rlhip_per_writeback_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}),
+              tree.ptr, n_leaves, key.ptr, td.ptr, n, eps, alpha, out.ptr, stream()))
+"one vec-step of a DQN learner over prioritized replay as one call (the caller fills `a`; no Julia loop drives it yet: INTEGRATION.md)"
+dqn_vec_step_per!(a::DqnPerStepArgs) =
+    chk(ccall((:rlhip_dqn_vec_step_per_f32, LIB), Int32, (Ref{DqnPerStepArgs}, Ptr{Cvoid}), a, stream()))
 "trajectory[:priority, keys] = p   (0-based physical leaf keys from the sampler)"
 set_priority!(tree::DevBuf{Float32}, n_leaves, key::DevBuf{Int64}, p::DevBuf{Float32}, n) =
     chk(ccall((:rlhip_sumtree_update, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}),

@@ -9,7 +9,7 @@ from .envs import (AcrobotRK4Env, CartPoleEnv, ContinuousMountainCarEnv, HipVecE
 from .core import (Agent, BatchStepsPerEpisode, ComposedHook, DeviceEpisodeStats, DoEveryNSteps, EmptyHook,  # noqa: F401
                    PPOAgent, RandomPolicy, StepsPerEpisode, StopAfterNEpisodes, StopAfterNSeconds,
                    StopAfterNSteps, StopIfAll, StopIfAny, TimePerStep, TotalBatchRewardPerEpisode, run,
-                   run_fused_dqn, run_fused_dqn_folded, run_fused_ppo)
+                   run_fused_dqn, run_fused_dqn_folded, run_fused_dqn_prioritized, run_fused_ppo)
 from .dqn import (DQNLearner, DuelingApproximator, EpsilonGreedyExplorer, GreedyExplorer, HipApproximator,  # noqa: F401
                   QBasedPolicy, TargetNetwork)
 from .explorers import (BatchExplorer, GumbelSoftmaxExplorer, UCBExplorer, WeightedExplorer,  # noqa: F401

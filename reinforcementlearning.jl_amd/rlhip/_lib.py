@@ -90,6 +90,12 @@ class DqnFoldStepArgs(C.Structure):
                 ("td", vp), ("fold_workspace", vp), ("dueling_params", vp), ("target_dueling", vp), ("grad_dueling", vp)]
 
 
+class DqnPerStepArgs(C.Structure):
+    """rlhip_dqn_per_step_args (include/rlhip.h)"""
+    _fields_ = [("fold", DqnFoldStepArgs), ("tree", vp), ("default_priority", f32), ("per_eps", f32), ("per_alpha", f32),
+                ("per_beta", f32), ("key", vp), ("prio", vp), ("is_weights", vp), ("priority_out", vp)]
+
+
 class Ring(C.Structure):
     _fields_ = [(n, i64) for n in ("capacity", "n_env", "obs_dim", "head_sa", "len_sa", "head_rt",
                                    "len_rt")] + \
@@ -202,6 +208,7 @@ _PROTOS = {
     "rlhip_dqn_vec_step_f32": (i32, [vp, vp]),
     "rlhip_dqn_sample_fold_f32": (i32, [P(Ring), i64, i32, i32, f32, u64, u32, i64, i64, i32, vp, vp, P(Ring), vp, vp, vp]),
     "rlhip_dqn_vec_step_fold_f32": (i32, [vp, vp]),
+    "rlhip_dqn_vec_step_per_f32": (i32, [vp, vp]),
     "rlhip_p2p_alloc": (i32, [i64, P(vp)]),
     "rlhip_p2p_free": (i32, [vp]),
     "rlhip_p2p_export": (i32, [vp, vp]),
@@ -241,6 +248,7 @@ _PROTOS = {
     "rlhip_sumtree_update": (i32, [vp, i64, vp, vp, i64, vp]),
     "rlhip_sumtree_sample": (i32, [vp, i64, i64, u64, u32, vp, vp, vp]),
     "rlhip_per_priority_f32": (i32, [vp, i64, f32, f32, vp, vp]),
+    "rlhip_per_writeback_f32": (i32, [vp, i64, vp, vp, i64, f32, f32, vp, vp]),
     "rlhip_per_is_weights_f32": (i32, [vp, i64, f32, vp, vp]),
     "rlhip_ring_push_priority": (i32, [P(Ring), vp, f32, vp]),
     "rlhip_ring_sample_prioritized": (i32, [P(Ring), vp, i64, u64, u32, vp, vp, vp, vp]),

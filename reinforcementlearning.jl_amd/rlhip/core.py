@@ -428,11 +428,12 @@ def _fused_dqn_begin(agent, env, stop_condition, hook, a):
     return stop_condition, hook
 
 
-def _fused_dqn_steps(agent, env, stop_condition, hook, name, args, a, gate, per_step):
-    """the loop of both fused DQN forms and its epilogue: one call of `name` per vec-step on `args` (passed by reference), whose
+def _fused_dqn_steps(agent, env, stop_condition, hook, name, args, a, gate, per_step, before_call=None):
+    """the loop of every fused DQN form and its epilogue: one call of `name` per vec-step on `args` (passed by reference), whose
     rlhip_dqn_step_args part `a` receives the per-step fields.  `gate(trajectory, count)` is `do_update`, asked with `per_step` times
     the number of vec-steps the trajectory holds once the step's push has happened (per_step = n_env: the gate counts transitions);
-    it advances the learner's vec-step counter."""
+    it advances the learner's vec-step counter.  `before_call()`, when given, sets a form's own per-step fields once those of `a`
+    are in place."""
     import ctypes as C
 
     from ._lib import call
@@ -451,6 +452,8 @@ def _fused_dqn_steps(agent, env, stop_condition, hook, name, args, a, gate, per_
         a.do_update = int(gate(traj, min(len(traces) + 1, traces.capacity) * per_step))  # warm-up, update_freq, sample / insert controller
         a.draw_ctr = learner.draw_ctr
         a.do_sync = int(a.do_update and (tn.n_optimise + 1) % tn.sync_freq == 0)
+        if before_call is not None:
+            before_call()
         call(name, C.byref(args), s)
         if a.do_update:
             learner.draw_ctr += 1
@@ -498,7 +501,8 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
     DuelingApproximator, any combination -- and the plain learner.  The whole loop body is ONE C-ABI call per vec-step
     (rlhip_dqn_vec_step_fold_f32): the kernels, their order and the counters are those of `run`, so parameters, optimiser state,
     trajectory and explorer end bit-identical to the per-stage loop (tests/test_gpu_fused_folds.py) and either loop may continue
-    the other.  Prioritized traces, tie-breaking explorers, continuous / Float64 envs and a process group stay on `run`."""
+    the other.  Prioritized traces run on run_fused_dqn_prioritized; tie-breaking explorers, continuous / Float64 envs and a process
+    group stay on `run`."""
     import ctypes as C
 
     from . import _lib
@@ -511,7 +515,7 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
     traces = traj.container
     if hasattr(traces, "sample_prioritized"):
         raise NotImplementedError("fused folded DQN step: uniform replay only; prioritized traces (CircularPrioritizedTraces) run "
-                                  "on the per-stage loop, rlhip.run")
+                                  "on rlhip.run_fused_dqn_prioritized or the per-stage loop, rlhip.run")
     if ex.is_break_tie:
         raise NotImplementedError("fused folded DQN step: plain eps-greedy only; a tie-breaking explorer (is_break_tie) runs on the "
                                   "per-stage loop, rlhip.run")
@@ -534,6 +538,92 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
         f.dueling_params, f.target_dueling, f.grad_dueling = ptr(net.dueling_params), ptr(tn.target_dueling), ptr(net._grad.t)
     return _fused_dqn_steps(agent, env, stop_condition, hook, "rlhip_dqn_vec_step_fold_f32", f, f.base,
                             functools.partial(_folded_update_gate, learner), 1)
+
+
+class _PerStepScratch:
+    """the fused prioritized step's own buffers on a learner, rewritten in full by every update (rlhip/checkpoint.py leaves them out)"""
+    checkpoint_scratch = True
+
+    def __init__(self, batch, device):
+        self.batch = batch
+        self.td_raw = torch.zeros(batch, dtype=torch.float32, device=device)  # |Q(s,a) - y|: the write-back's input
+        self.idx = torch.empty(batch, dtype=torch.int64, device=device)
+        self.key = torch.empty(batch, dtype=torch.int64, device=device)
+        self.prio = torch.empty(batch, dtype=torch.float32, device=device)
+
+
+def run_fused_dqn_prioritized(agent, env, stop_condition=None, hook=None):
+    """`run_fused_dqn_folded` for learners over prioritized replay: DQNLearner on CircularPrioritizedTraces, 1-step or n-step, plain or
+    Double DQN targets, plain or dueling nets, with or without importance-sampling weights (`per_beta`, a number or a callable
+    n_updates -> beta).  The whole loop body is ONE C-ABI call per vec-step (rlhip_dqn_vec_step_per_f32), with the priority power and
+    the sum-tree write-back as one launch (rlhip_per_writeback_f32): the kernels, their order and the counters are those of `run`, so
+    parameters, optimiser state, trajectory, sum-tree and explorer end bit-identical to the per-stage loop
+    (tests/test_gpu_fused_per.py) and either loop may continue the other.  `learner.td` holds the written-back priorities, as the
+    per-stage learner leaves them.  Uniform traces run on run_fused_dqn_folded; tie-breaking explorers, continuous / Float64 envs
+    and a process group stay on `run`."""
+    import ctypes as C
+
+    from . import _lib
+    from .ops import ptr
+
+    policy, traj = agent.policy, agent.trajectory
+    learner, ex = policy.learner, policy.explorer
+    tn = learner.approximator
+    net = tn.network
+    traces = traj.container
+    if not hasattr(traces, "sample_prioritized"):
+        raise NotImplementedError("fused prioritized DQN step: prioritized traces (CircularPrioritizedTraces) only; uniform replay runs "
+                                  "on rlhip.run_fused_dqn_folded")
+    if ex.is_break_tie:
+        raise NotImplementedError("fused prioritized DQN step: plain eps-greedy only; a tie-breaking explorer (is_break_tie) runs on "
+                                  "the per-stage loop, rlhip.run")
+    if env.continuous or env.is_f64:
+        raise NotImplementedError("fused prioritized DQN step: Float32 discrete envs only; a continuous or Float64 env runs on the "
+                                  "per-stage loop, rlhip.run")
+    if learner.process_group is not None:
+        raise NotImplementedError("fused prioritized DQN step: 1 GPU; a learner with a process group (process_group) runs on the "
+                                  "per-stage loop, rlhip.run")
+    n_step, double = int(getattr(learner, "n_step", 1)), bool(getattr(learner, "double_dqn", False))
+    if getattr(traces, "n_step", 1) != n_step:
+        raise ValueError(f"DQNLearner(n_step = {n_step}) needs CircularPrioritizedTraces(..., n_step = {n_step}): "
+                         f"these traces mask windows of {getattr(traces, 'n_step', 1)}")
+    dueling = getattr(net, "dueling_params", None) is not None
+    p = _lib.DqnPerStepArgs()
+    f = p.fold
+    stop_condition, hook = _fused_dqn_begin(agent, env, stop_condition, hook, f.base)
+    b, dev = learner.batchsize, traces.state.device
+    sc = getattr(learner, "_per_step", None)
+    if sc is None or sc.batch != b or sc.td_raw.device != dev:
+        sc = learner._per_step = _PerStepScratch(b, dev)
+    idx, key, prio = sc.idx, sc.key, sc.prio
+    if n_step > 1 or double:
+        folded, fidx, iota, ws = _folded_scratch(learner, traces, net)
+        f.folded, f.iota = C.addressof(folded.rb), ptr(iota)
+        f.fold_workspace = ptr(ws) if ws is not None else None
+    if n_step > 1:  # the draw buffers of NStepBatchSampler.sample_fold_prioritized: the per-stage learner leaves all three on itself
+        smp = learner._nstep
+        if smp._draw is None or smp._draw[0].numel() != b or smp._draw[0].device != dev:
+            smp._draw = (idx, key, prio)
+        idx, key, prio = smp._draw
+        smp.key, smp.priority = key, prio
+        learner._idx = idx
+    elif double:  # the indices the Double DQN fold took
+        learner._idx = idx = fidx
+    learner._key, learner._prio = key, prio
+    f.n_step, f.double_dqn, f.td, f.idx = n_step, int(double), ptr(sc.td_raw), ptr(idx)
+    if dueling:
+        f.dueling_params, f.target_dueling, f.grad_dueling = ptr(net.dueling_params), ptr(tn.target_dueling), ptr(net._grad.t)
+    p.tree, p.default_priority = ptr(traces.priorities), traces.default_priority
+    p.per_eps, p.per_alpha = learner.per_eps, learner.per_alpha
+    p.key, p.prio, p.is_weights, p.priority_out = ptr(key), ptr(prio), ptr(learner.is_weights), ptr(learner.td)
+
+    def per_step_fields():  # _is_weights_'s beta for the update this step makes: a schedule is asked once per update, as there
+        if f.base.do_update:
+            beta = float(learner.per_beta(learner.n_updates)) if callable(learner.per_beta) else float(learner.per_beta)
+            p.per_beta = beta if beta > 0.0 else 0.0
+
+    return _fused_dqn_steps(agent, env, stop_condition, hook, "rlhip_dqn_vec_step_per_f32", p, f.base,
+                            functools.partial(_folded_update_gate, learner), 1, per_step_fields)
 
 
 def run_fused_ppo(policy, env, n_updates, hook=None):
