@@ -21,15 +21,10 @@
 //
 // Three-layer nets (bf16 MFMA forward): composition -- gather s' into the workspace, the shipped forward (rlhip_dqn3_plan_f32,
 // actions = NULL) once per net, one select-and-write kernel.  No MFMA code lives in this file.
-#include "mlp_device.h"
-#include "ring_device.h"
+#include "fold_device.h"
+#include "fold_host.h"
 
 namespace rlhip {
-
-constexpr int FD_TILE = 64;
-constexpr int FD_THREADS = 1024;
-constexpr int FD_MAX_BLOCKS = 512;
-constexpr int FD_HMAX = 256;
 
 struct FoldDoubleArgs {
     RingRecs ring;
@@ -43,66 +38,35 @@ struct FoldDoubleArgs {
     float gamma;
 };
 
-// y = r + gamma * (1 - t) * Qt(s')[a*], a* = findmax(Q(s')) over the first `na` values (the first maximum wins: strict >): the
-// gradient kernels' target line with Qt(s')[a*] in the place of the maximum.  (Scalars, not arrays: nothing to index at run time.)
-__device__ __forceinline__ float double_target(float r, uint32_t term, float gamma, float q0, float q1, float q2, float q3, float t0,
-                                               float t1, float t2, float t3, int na) {
-    float m = q0, v = t0;
-    if (na > 1 && q1 > m) m = q1, v = t1;
-    if (na > 2 && q2 > m) m = q2, v = t2;
-    if (na > 3 && q3 > m) m = q3, v = t3;
-    const float cont = term ? 0.f : 1.f;
-    return r + gamma * cont * v;
-}
-
 template <int NS, int ACT>
-__global__ __launch_bounds__(FD_THREADS) void dqn_fold_double_kernel(FoldDoubleArgs g) {
-    // l_rec[net][j] = {W1[j, 0..3]}, {b1[j], W2[0..2, j]}, {W2[3, j], -, -, -} (rows beyond NS / na are zeros): dqn_grad_kernel's layout
-    __shared__ float4 l_rec[2][FD_HMAX][3];
-    __shared__ nt_u32x4 l_s[FD_TILE], l_w[FD_TILE], l_sn[FD_TILE];  // the three live quarters of each sample's record
+__global__ __launch_bounds__(FOLD_THREADS) void dqn_fold_double_kernel(FoldDoubleArgs g) {
+    __shared__ FoldNets l_rec;
+    __shared__ nt_u32x4 l_s[FOLD_TILE], l_w[FOLD_TILE], l_sn[FOLD_TILE];  // the three live quarters of each sample's record
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int row = lane >> 4, c = lane & 15;
     const int h = g.h, na = g.na;
-    const float* b2 = g.params + h * NS + h + na * h;
-    const float* tb2 = g.tparams + h * NS + h + na * h;
     const int smp = 4 * w + row;  // this row's sample of the tile
     bool staged = false;
 
     for (int tile = blockIdx.x; tile < g.num_tiles; tile += gridDim.x) {
-        float bq[MAXO], btq[MAXO];  // output biases: requested first, in flight across the staging and the barrier
-#pragma unroll
-        for (int o = 0; o < MAXO; ++o) {
-            bq[o] = (o < na) ? b2[o] : 0.f;
-            btq[o] = (o < na) ? tb2[o] : 0.f;
-        }
+        float bq[MAXO], btq[MAXO];
+        fold_load_out_biases<NS>(g.params, g.tparams, h, na, bq, btq);
         nt_u32x4 rs = {0u, 0u, 0u, 0u}, rw = rs, rsn = rs;
-        if (tid < FD_TILE) {
-            const int64_t b = (int64_t)tile * FD_TILE + tid;
+        if (tid < FOLD_TILE) {
+            const int64_t b = (int64_t)tile * FOLD_TILE + tid;
             const int64_t fj = g.idx[b < g.batch ? b : 0];
             const uint8_t* r0 = g.ring.rec + ring_record_offset(g.ring, fj);  // one 64-byte record = one fabric request per sample
             rs = *reinterpret_cast<const nt_u32x4*>(r0);
             rw = *reinterpret_cast<const nt_u32x4*>(r0 + 16);
             rsn = *reinterpret_cast<const nt_u32x4*>(r0 + 32);
         }
-        if (!staged) {  // both networks -> LDS once per workgroup, while the gather is in flight
+        if (!staged) {  // once per workgroup, while the gather is in flight
             staged = true;
-            for (int q = tid; q < 2 * h; q += FD_THREADS) {
-                const int net = q >= h ? 1 : 0, u = q - net * h;
-                const float* P = net ? g.tparams : g.params;
-                float w1[4] = {0.f, 0.f, 0.f, 0.f}, w2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < NS; ++k) w1[k] = P[u + h * k];
-#pragma unroll
-                for (int o = 0; o < MAXO; ++o)
-                    if (o < na) w2[o] = P[h * NS + h + o + na * u];
-                l_rec[net][u][0] = make_float4(w1[0], w1[1], w1[2], w1[3]);
-                l_rec[net][u][1] = make_float4(P[h * NS + u], w2[0], w2[1], w2[2]);
-                l_rec[net][u][2] = make_float4(w2[3], 0.f, 0.f, 0.f);
-            }
+            fold_stage_two_nets<NS>(l_rec, g.params, g.tparams, h, na, tid);
         }
-        if (tid < FD_TILE) {
+        if (tid < FOLD_TILE) {
             l_s[tid] = rs;
             l_w[tid] = rw;
             l_sn[tid] = rsn;
@@ -110,51 +74,11 @@ __global__ __launch_bounds__(FD_THREADS) void dqn_fold_double_kernel(FoldDoubleA
         __syncthreads();
         {
             const nt_u32x4 un = l_sn[smp], uw = l_w[smp];
-            const float xn[4] = {__uint_as_float(un[0]), __uint_as_float(un[1]), __uint_as_float(un[2]), __uint_as_float(un[3])};
-            float acc[MAXO] = {0.f, 0.f, 0.f, 0.f}, acn[MAXO] = {0.f, 0.f, 0.f, 0.f};  // online / target net, both on s'
-#pragma unroll 2
-            for (int jj = c; jj < h; jj += 16) {
-                const float4 a0 = l_rec[0][jj][0], a1 = l_rec[0][jj][1], c0 = l_rec[1][jj][0], c1 = l_rec[1][jj][1];
-                const float wa[4] = {a0.x, a0.y, a0.z, a0.w}, wc[4] = {c0.x, c0.y, c0.z, c0.w};
-                float z = a1.x, zn = c1.x;
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    z = fmaf(wa[k], xn[k], z);
-                    zn = fmaf(wc[k], xn[k], zn);
-                }
-                const float hv = act_fwd_t<ACT>(z), hn = act_fwd_t<ACT>(zn);
-                acc[0] = fmaf(a1.y, hv, acc[0]);
-                acn[0] = fmaf(c1.y, hn, acn[0]);
-                acc[1] = fmaf(a1.z, hv, acc[1]);  // (rows o >= na are staged as zeros)
-                acn[1] = fmaf(c1.z, hn, acn[1]);
-                if (na > 2) {  // (uniform)
-                    acc[2] = fmaf(a1.w, hv, acc[2]);
-                    acn[2] = fmaf(c1.w, hn, acn[2]);
-                }
-                if (na == 4) {
-                    acc[3] = fmaf(l_rec[0][jj][2].x, hv, acc[3]);
-                    acn[3] = fmaf(l_rec[1][jj][2].x, hn, acn[3]);
-                }
-            }
             float q[MAXO], qt[MAXO];
-#pragma unroll
-            for (int o = 0; o < MAXO; ++o) {
-                q[o] = 0.f, qt[o] = 0.f;
-                if (o < na) {  // (uniform)
-                    q[o] = group_sum_dpp<16>(acc[o]) + bq[o];
-                    qt[o] = group_sum_dpp<16>(acn[o]) + btq[o];
-                }
-            }
+            fold_two_net_q<NS, ACT>(l_rec, un, h, na, c, bq, btq, q, qt);
             const float y = double_target(__uint_as_float(uw[1]), uw[2] & 0xffu, g.gamma, q[0], q[1], q[2], q[3], qt[0], qt[1], qt[2], qt[3], na);
-            const int64_t b = (int64_t)tile * FD_TILE + smp;
-            if (b < g.batch && c < 4) {  // lanes 0..3 of the row: the four quarters of one 64-byte line, one store instruction
-                nt_u32x4 o4 = {0u, 0u, 0u, 0u};
-                if (c == 0) o4 = l_s[smp];
-                else if (c == 1) o4 = nt_u32x4{uw[0], __float_as_uint(y), 1u, 0u};
-                else if (c == 2) o4 = un;
-                *reinterpret_cast<nt_u32x4*>(g.out + b * RING_REC_BYTES + 16 * c) = o4;
-                if (c == 0 && g.iota) g.iota[b] = b;
-            }
+            const int64_t b = (int64_t)tile * FOLD_TILE + smp;
+            if (b < g.batch && c < 4) fold_store_row(g.out, g.iota, b, c, l_s[smp], uw[0], y, 1u, un);
         }
         __syncthreads();  // the next tile overwrites l_s / l_w / l_sn
     }
@@ -191,12 +115,7 @@ __global__ __launch_bounds__(256) void fold_double_select_kernel(RingRecs ring, 
             qt[o] = q_tg[(int64_t)o * batch + b];
         }
     const float y = double_target(__uint_as_float(rw[1]), rw[2] & 0xffu, gamma, q[0], q[1], q[2], q[3], qt[0], qt[1], qt[2], qt[3], na);
-    uint8_t* o = out + b * RING_REC_BYTES;
-    *reinterpret_cast<nt_u32x4*>(o) = rs;
-    *reinterpret_cast<nt_u32x4*>(o + 16) = nt_u32x4{rw[0], __float_as_uint(y), 1u, 0u};
-    *reinterpret_cast<nt_u32x4*>(o + 32) = rsn;
-    *reinterpret_cast<nt_u32x4*>(o + 48) = nt_u32x4{0u, 0u, 0u, 0u};
-    if (iota) iota[b] = b;
+    fold_store_record(out, iota, b, rs, rw[0], y, 1u, rsn);
 }
 
 static inline int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
@@ -208,20 +127,12 @@ static int32_t fold_double_check(const rlhip_ring* rb, const int64_t* idx, int64
     RLHIP_REQUIRE(rb->layout == RLHIP_RING_RECORDS && rb->elem_bytes == 4,
                   "the Double DQN fold is defined for record rings (Float32 observations, obs_dim <= 4)");
     RLHIP_REQUIRE(rb->obs_dim >= 2 && rb->obs_dim <= 4, "the DQN learners take obs_dim 2..4");
-    RLHIP_REQUIRE(folded->layout == RLHIP_RING_RECORDS && folded->state != nullptr && folded->capacity >= 1 && folded->n_env == batch &&
-                      folded->obs_dim == rb->obs_dim,
-                  "`folded` must be a record ring initialised with rlhip_ring_init(capacity >= 1, n_env = batch, the source's obs_dim)");
+    const int32_t rc = check_folded_dest(rb, folded, batch, /*may_alias=*/true);
+    if (rc) return rc;
     RLHIP_REQUIRE(folded->state != rb->state || (rb->n_env == batch && rb->head_sa == 0 && rb->len_rt == 1),
                   "in place (`folded` = the source) only on an already folded ring: one stored vec-step of `batch` envs, idx = its iota");
     RLHIP_REQUIRE(rb->len_rt >= 1, "cannot sample from an empty trajectory");
     return RLHIP_OK;
-}
-
-static void mark_folded(rlhip_ring* folded) {  // slot 0 now holds `batch` complete transitions: one stored vec-step
-    folded->head_sa = 0;
-    folded->len_sa = 2;
-    folded->head_rt = 0;
-    folded->len_rt = 1;
 }
 
 }  // namespace rlhip
@@ -244,9 +155,8 @@ int32_t rlhip_dqn_fold_double_f32(const rlhip_ring* rb, int64_t h, int64_t na, i
     int32_t rc = fold_double_check(rb, idx, batch, folded);
     if (rc) return rc;
     RLHIP_REQUIRE(params && target_params, "NULL argument");
-    RLHIP_REQUIRE(h >= 4 && h <= FD_HMAX && h % 4 == 0, "hidden must be a multiple of 4, <= 256");
-    RLHIP_REQUIRE(na >= 1 && na <= MAXO, "na must be <= 4");
-    RLHIP_REQUIRE(act == 0 || act == 1, "act must be 0 (relu) or 1 (tanh)");
+    rc = check_mlp2_fold_net(h, na, act);
+    if (rc) return rc;
     RLHIP_CHECK_GATHER_INDICES(rb, idx, batch, stream);
     FoldDoubleArgs g;
     g.ring = {(const uint8_t*)rb->state, rb->capacity, rb->n_env, rb->head_sa};
@@ -258,17 +168,17 @@ int32_t rlhip_dqn_fold_double_f32(const rlhip_ring* rb, int64_t h, int64_t na, i
     g.iota = iota_out;
     g.h = (int)h;
     g.na = (int)na;
-    const int64_t tiles = (batch + FD_TILE - 1) / FD_TILE;
+    const int64_t tiles = (batch + FOLD_TILE - 1) / FOLD_TILE;
     RLHIP_REQUIRE(tiles <= INT32_MAX, "batch too large");
     g.num_tiles = (int)tiles;
     g.gamma = gamma_eff;
-    const int nb = g.num_tiles < FD_MAX_BLOCKS ? g.num_tiles : FD_MAX_BLOCKS;
+    const int nb = g.num_tiles < FOLD_MAX_BLOCKS ? g.num_tiles : FOLD_MAX_BLOCKS;
     const int ns = (int)rb->obs_dim;
     hipStream_t s = as_stream(stream);
 #define LAUNCH_FD(NS_)                                                                                              \
     do {                                                                                                            \
-        if (act == 0) hipLaunchKernelGGL((dqn_fold_double_kernel<NS_, 0>), dim3(nb), dim3(FD_THREADS), 0, s, g);    \
-        else hipLaunchKernelGGL((dqn_fold_double_kernel<NS_, 1>), dim3(nb), dim3(FD_THREADS), 0, s, g);             \
+        if (act == 0) hipLaunchKernelGGL((dqn_fold_double_kernel<NS_, 0>), dim3(nb), dim3(FOLD_THREADS), 0, s, g);    \
+        else hipLaunchKernelGGL((dqn_fold_double_kernel<NS_, 1>), dim3(nb), dim3(FOLD_THREADS), 0, s, g);             \
     } while (0)
     if (ns == 4) LAUNCH_FD(4);
     else if (ns == 3) LAUNCH_FD(3);

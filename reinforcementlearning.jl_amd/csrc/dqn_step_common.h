@@ -4,6 +4,7 @@
 // dqn_step_per.hip (rlhip_dqn_vec_step_per_f32); host code only.
 #pragma once
 #include "common.h"
+#include "fold_host.h"
 
 namespace rlhip {
 
@@ -17,7 +18,7 @@ static inline int32_t check_fold_step(const rlhip_dqn_fold_step_args* f, bool fo
                   "learner buffers missing");
     const int64_t ns = rlhip_env_obs_dim(a->kind);
     RLHIP_REQUIRE(ns == a->ring->obs_dim && a->n == a->ring->n_env, "ring geometry does not match the env");
-    RLHIP_REQUIRE(f->n_step >= 1 && f->n_step <= 32, "n_step must be in 1..32");
+    RLHIP_REQUIRE(f->n_step >= 1 && f->n_step <= FOLD_MAX_NSTEP, "n_step must be in 1..32");
     RLHIP_REQUIRE(f->double_dqn == 0 || f->double_dqn == 1, "double_dqn must be 0 or 1");
     RLHIP_REQUIRE((f->dueling_params != nullptr) == (f->target_dueling != nullptr) &&
                       (f->dueling_params != nullptr) == (f->grad_dueling != nullptr),
@@ -33,13 +34,13 @@ static inline int32_t check_fold_step(const rlhip_dqn_fold_step_args* f, bool fo
                   "`folded` must be a record ring initialised with rlhip_ring_init(capacity >= 1, n_env = batch, the env's obs_dim)");
     RLHIP_REQUIRE(f->folded->state != a->ring->state, "`folded` must not alias the trajectory");
     if (a->layers == 2) {
-        RLHIP_REQUIRE(a->h >= 4 && a->h <= 256 && a->h % 4 == 0, "hidden must be a multiple of 4, <= 256");
-        RLHIP_REQUIRE(a->na >= 1 && a->na <= 4, "na must be <= 4");
+        const int32_t rc = check_mlp2_fold_net(a->h, a->na, a->act);
+        if (rc) return rc;
     } else {
         RLHIP_REQUIRE(a->h == 128 || a->h == 256, "the MFMA Q-network path is built for hidden = 128 or 256");
         RLHIP_REQUIRE(!f->double_dqn || !a->do_update || f->fold_workspace, "the 3-layer Double DQN fold needs fold_workspace");
+        RLHIP_REQUIRE(a->act == 0 || a->act == 1, "act must be 0 (relu) or 1 (tanh)");
     }
-    RLHIP_REQUIRE(a->act == 0 || a->act == 1, "act must be 0 (relu) or 1 (tanh)");
     if (a->do_update) {  // the ring as it will be after this call's push
         const int64_t len_after = a->ring->len_rt < a->ring->capacity ? a->ring->len_rt + 1 : a->ring->capacity;
         RLHIP_REQUIRE(a->ring->len_sa == a->ring->len_rt + 1, "push the first state (rlhip_ring_push_state) before the first vec-step");

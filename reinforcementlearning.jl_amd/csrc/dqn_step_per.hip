@@ -28,18 +28,20 @@ int32_t check_per_step(const rlhip_dqn_per_step_args* p, bool folds, bool duelin
     const rlhip_dqn_step_args* a = &f->base;
     int32_t rc = check_fold_step(f, folds, dueling);
     if (rc) return rc;
-    // what every gradient entry point of a prioritized learner asks of the trajectory and the net, folded batch or not: asked here,
-    // in front of the push
-    const int64_t ns = rlhip_env_obs_dim(a->kind);
-    RLHIP_REQUIRE(a->ring->layout == RLHIP_RING_RECORDS && a->ring->elem_bytes == 4 && ns >= 2 && ns <= 4,
-                  "the prioritized step is defined for record rings (Float32 observations, obs_dim 2..4)");
-    if (a->layers == 2) {
-        RLHIP_REQUIRE(a->h >= 4 && a->h <= 256 && a->h % 4 == 0, "hidden must be a multiple of 4, <= 256");
-        RLHIP_REQUIRE(a->na >= 1 && a->na <= 4, "na must be <= 4");
-    } else {
-        RLHIP_REQUIRE(a->h == 128 || a->h == 256, "the MFMA Q-network path is built for hidden = 128 or 256");
+    // what every gradient entry point of a prioritized learner asks of the trajectory and the net, asked in front of the push: of a
+    // folded batch check_fold_step has asked it already
+    if (!folds) {
+        const int64_t ns = rlhip_env_obs_dim(a->kind);
+        RLHIP_REQUIRE(a->ring->layout == RLHIP_RING_RECORDS && a->ring->elem_bytes == 4 && ns >= 2 && ns <= 4,
+                      "the prioritized step is defined for record rings (Float32 observations, obs_dim 2..4)");
+        if (a->layers == 2) {
+            rc = check_mlp2_fold_net(a->h, a->na, a->act);
+            if (rc) return rc;
+        } else {
+            RLHIP_REQUIRE(a->h == 128 || a->h == 256, "the MFMA Q-network path is built for hidden = 128 or 256");
+            RLHIP_REQUIRE(a->act == 0 || a->act == 1, "act must be 0 (relu) or 1 (tanh)");
+        }
     }
-    RLHIP_REQUIRE(a->act == 0 || a->act == 1, "act must be 0 (relu) or 1 (tanh)");
     RLHIP_REQUIRE(p->tree != nullptr, "NULL tree");
     RLHIP_REQUIRE(p->default_priority > 0.0f, "default_priority must be > 0");
     RLHIP_REQUIRE(p->per_eps >= 0.0f && p->per_alpha >= 0.0f && p->per_beta >= 0.0f, "per_eps, per_alpha and per_beta must be >= 0");

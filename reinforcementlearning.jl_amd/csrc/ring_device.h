@@ -63,6 +63,36 @@ __device__ __forceinline__ int64_t ring_record_offset(const RingRecs& rb, int64_
     return (ps * rb.n_env + e) * RING_REC_BYTES;
 }
 
+// x = q * n_env + r with 0 <= r < n_env -- a flat logical index into (li, e), a sum-tree key into (rt frame, e) -- by the same rule:
+// no 64-bit division where 32 bits do
+__device__ __forceinline__ void ring_split_index(int64_t x, int64_t n_env, int64_t& q, int64_t& r) {
+    if (((uint64_t)x | (uint64_t)n_env) >> 32) {
+        q = x / n_env;
+        r = x - q * n_env;
+    } else {
+        const uint32_t q32 = (uint32_t)x / (uint32_t)n_env;
+        q = q32;
+        r = (uint32_t)x - q32 * (uint32_t)n_env;
+    }
+}
+
+// A cursor over the records of one env, oldest to newest: built on logical step li (state slot (head_sa + li) mod (capacity + 1):
+// li < capacity, so the sum wraps at most once), stepped one slot at a time with a single wrap -- no division per step.
+struct RingCursor {
+    RingRecs rb;
+    int64_t e, ps;
+    __device__ __forceinline__ const uint8_t* record() const { return rb.rec + (ps * rb.n_env + e) * RING_REC_BYTES; }
+    __device__ __forceinline__ const uint8_t* next() {
+        ps = (ps == rb.capacity) ? 0 : ps + 1;
+        return record();
+    }
+};
+__device__ __forceinline__ RingCursor ring_cursor(const RingRecs& rb, int64_t li, int64_t e) {
+    int64_t ps = rb.head_sa + li;
+    if (ps > rb.capacity) ps -= rb.capacity + 1;
+    return {rb, e, ps};
+}
+
 union RingChunk {  // one 16-byte quarter of a record
     nt_u32x4 u;
     float f[4];

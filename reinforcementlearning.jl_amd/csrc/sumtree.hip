@@ -102,10 +102,7 @@ __global__ __launch_bounds__(256) void sumtree_sample_kernel(const float* __rest
                                                              float* __restrict__ prio_out) {
     int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
-    u32x4 w = philox4x32_10(seed, (uint32_t)b, 0, draw_ctr, TAG_SAMPLER);
-    float v = u01_f32(w.z) * tree[1];  // rand(rng, Float32) * t.tree[1]
-    int64_t leaf = sumtree_descend(tree, P, v);
-    if (leaf >= n_leaves) leaf = n_leaves - 1;
+    const int64_t leaf = sumtree_draw(tree, P, n_leaves, seed, b, draw_ctr);
     if (key_out) key_out[b] = leaf;
     if (prio_out) prio_out[b] = tree[P + leaf];
     if (RING) {

@@ -1,6 +1,7 @@
 // sumtree_device.h -- the one-wavefront priority write-back (<= 64 keys) as a device function, shared by its own launch
 // (sumtree.hip: rlhip_sumtree_update), by the prologue of the fused "update -> draw -> gather" launch (ring.hip, round 6) and by the
-// fused power + write-back (per_writeback.hip); the value sources of a write-back; and the descent of one prioritized draw.
+// fused power + write-back (per_writeback.hip); the value sources of a write-back; and one prioritized draw (sumtree_draw: sumtree_sample_kernel
+// and the prioritized n-step launch of per_nstep.hip).
 #pragma once
 #include "common.h"
 
@@ -42,7 +43,8 @@ struct SmallUpdateLds {
 };
 
 // rand(rng, t)'s descent for one draw, `v <= left ? left : (v -= left; right)`, never into a zero-sum subtree while the sibling has
-// mass: log2(P) dependent 8-byte reads.  Shared by sumtree_sample_kernel (sumtree.hip) and the prioritized n-step launch (per_nstep.hip).
+// mass: log2(P) dependent 8-byte reads.  (The fused draw + gather of ring.hip restates it over its own loads: after an in-launch
+// write-back those are device-scope.)
 __device__ __forceinline__ int64_t sumtree_descend(const float* __restrict__ tree, int64_t P, float v) {
     int64_t node = 1;
     while (node < P) {
@@ -52,6 +54,23 @@ __device__ __forceinline__ int64_t sumtree_descend(const float* __restrict__ tre
         node = 2 * node + (right ? 1 : 0);
     }
     return node - P;
+}
+
+// the heap's leaf level starts at P = the smallest power of two >= n_leaves
+static inline int64_t pow2_ge(int64_t n) {
+    int64_t p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// One prioritized draw, sample b of draw `draw_ctr`: rand(rng, Float32) * t.tree[1] from the sample's Philox word, the descent, and
+// the clamp below n_leaves (a rounding walk into the zero padding of the last level) -> the leaf key.
+__device__ __forceinline__ int64_t sumtree_draw(const float* __restrict__ tree, int64_t P, int64_t n_leaves, uint64_t seed, int64_t b,
+                                                uint32_t draw_ctr) {
+    const u32x4 w = philox4x32_10(seed, (uint32_t)b, 0, draw_ctr, TAG_SAMPLER);
+    const float v = u01_f32(w.z) * tree[1];
+    const int64_t leaf = sumtree_descend(tree, P, v);
+    return leaf < n_leaves ? leaf : n_leaves - 1;
 }
 
 // tree stores: plain when the kernel boundary publishes them (COHERENT = false: the stand-alone launch), device-scope write-through

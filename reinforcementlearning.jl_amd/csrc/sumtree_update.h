@@ -7,11 +7,6 @@
 
 namespace rlhip {
 
-static inline int64_t pow2_ge(int64_t n) {
-    int64_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
 static inline int log2_of(int64_t p) {
     int l = 0;
     while ((1ll << l) < p) ++l;

@@ -52,6 +52,30 @@ def _source(rl):
     return _SRC["v"]
 
 
+def _source32(rl):
+    """the longest window: capacity 34 x 4 envs, 40 pushes of made-up transitions (head_sa = 6, so a 32-step window crosses the state
+    trace's wrap slot).  Terminal flags written here: env 0 never ends, env e ends every 3 + 2 e pushes.  Built once."""
+    if "v32" not in _SRC:
+        n_env, cap = 4, 34
+        rng = np.random.default_rng(32)
+        tr = rl.CircularArraySARTSTraces(capacity=cap, n_env=n_env, obs_dim=4)
+        oring = oracle.Ring(cap, n_env, 4)
+        obs = rng.standard_normal((4, n_env)).astype(np.float32)
+        tr.push_state_(dev(obs))
+        oring.push_state(obs)
+        for k in range(40):
+            nobs = rng.standard_normal((4, n_env)).astype(np.float32)
+            a = rng.integers(0, 2, n_env).astype(np.int32)
+            r = (rng.standard_normal(n_env) * 2).astype(np.float32)
+            t = np.array([e > 0 and k % (3 + 2 * e) == 0 for e in range(n_env)], np.uint8)
+            tr.push_transition_(dev(nobs), dev(a), dev(r), dev(t))
+            oring.push_transition(nobs, a, r, t)
+        torch.cuda.synchronize()
+        assert len(tr) == cap and tr.rb.head_sa == 6
+        _SRC["v32"] = (tr, oring, tr.records.clone())
+    return _SRC["v32"]
+
+
 def _nets(ns, h, na, seed=0):
     return oracle.mlp2_init(ns, h, na, 40 + seed, 0), oracle.mlp2_init(ns, h, na, 40 + seed, 1)
 
@@ -98,8 +122,8 @@ def _kernel(rl, tr, batch, n_step, double, h, na, act, p, pt, want_idx=True):
     return folded.records.view(torch.int32)[0].clone(), idx, iota
 
 
-def _check(rl, batch, n_step, double, h, na, act, nets=None):
-    tr, oring, snapshot = _source(rl)
+def _check(rl, batch, n_step, double, h, na, act, nets=None, source=_source):
+    tr, oring, snapshot = source(rl)
     p, pt = nets or _nets(4, h, na)
     ref, ridx, riota = _composition(rl, tr, batch, n_step, double, h, na, act, p, pt)
     if n_step > 1:  # the condition on the cases, on the reference alone: terminals INSIDE the windows
@@ -125,6 +149,22 @@ def test_sample_fold_equals_the_shipped_composition_byte_for_byte(n_step, double
     import rlhip as rl
 
     _check(rl, batch, n_step, double, h, na, act)
+
+
+@pytest.mark.parametrize("double", [0, 1])
+def test_sample_fold_at_the_longest_window(double):
+    """n_step = 32, the bound of the ABI, on a ring whose windows cross the wrap slot: the conditions on the drawn windows are asserted
+    on the composition's index list before the kernel runs (the composition is pinned to the oracle at n_step = 32 by test_gpu_nstep.py)"""
+    import rlhip as rl
+
+    n_step, batch = 32, 37
+    tr, oring, _ = _source32(rl)
+    idx = host(rl.NStepBatchSampler(n_step, GAMMA, batch, seed=SEED).sample_indices(tr, CTR))
+    env0 = idx[idx % tr.n_env == 0]
+    assert len(env0) >= 1 and _terminal_before_last(oring, env0, n_step) == 0, "no window of the full 32 steps (env 0) was drawn"
+    assert tr.rb.head_sa + env0.min() // tr.n_env <= tr.capacity < tr.rb.head_sa + env0.min() // tr.n_env + n_step, "no wrap inside it"
+    assert _terminal_before_last(oring, idx, n_step) > 0, "no drawn window is cut short by a terminal"
+    _check(rl, batch, n_step, double, 64, 2, 0, source=_source32)
 
 
 @pytest.mark.parametrize("n_step,na", [(1, 2), (3, 3), (5, 4)])

@@ -26,7 +26,7 @@ from test_gpu_bench_shapes import dev, host, note  # noqa: E402
 
 GAMMA = 0.97
 DEFAULT = 2.5
-TILE = 64  # PN_TILE of csrc/per_nstep.hip: batches 1, TILE, TILE + 1
+TILE = 64  # FOLD_TILE of csrc/fold_device.h: batches 1, TILE, TILE + 1
 
 
 def _bits(x):
@@ -112,6 +112,43 @@ def test_masked_push_and_fused_draw_fold_bit_exact(ns, n_step, pushes):
     d = b.sample(tr)
     assert np.array_equal(host(d["key"]), okey) and np.array_equal(host(d["priority"]), oprio) and b.draw_ctr == 4
     assert np.array_equal(host(d["reward"]), sarts[2]) and np.array_equal(host(d["action"]), sarts[1] + 1)
+
+
+def test_fused_draw_fold_at_the_longest_window():
+    """n_step = 32, the bound of the ABI: capacity 34 x 4 envs, 40 pushes (head_sa = 6: a 32-step window crosses the state trace's
+    wrap slot), terminal flags written here -- env 0 never ends, env e ends every 3 + 2 e pushes.  The one launch against the two
+    shipped launches byte for byte; the conditions on the drawn windows are asserted on the two launches' index list first
+    (rlhip_ring_fold_nstep is pinned to the oracle at n_step = 32 by tests/test_gpu_nstep.py)."""
+    import rlhip as rl
+
+    ns, n_step, batch, cap, n_env, pushes = 4, 32, 37, 34, 4, 40
+    rng = np.random.default_rng(32)
+    tr = rl.CircularPrioritizedTraces(capacity=cap, n_env=n_env, obs_dim=ns, default_priority=DEFAULT, n_step=n_step)
+    tr.push_state_(dev(rng.standard_normal((ns, n_env)).astype(np.float32)))
+    flags = np.array([[e > 0 and k % (3 + 2 * e) == 0 for e in range(n_env)] for k in range(pushes)], np.uint8)
+    for k in range(pushes):
+        tr.push_transition_(dev(rng.standard_normal((ns, n_env)).astype(np.float32)), dev(rng.integers(0, 2, n_env).astype(np.int32)),
+                            dev((rng.standard_normal(n_env) * 2).astype(np.float32)), dev(flags[k]))
+    assert len(tr) == cap and tr.rb.head_sa == 6
+    two = rl.NStepBatchSampler(n_step, GAMMA, batch, seed=9)
+    idx2 = two.sample_indices(tr, 3)            # rlhip_ring_sample_prioritized ...
+    folded2, iota2 = two.fold(tr, idx2)         # ... then rlhip_ring_fold_nstep
+    torch.cuda.synchronize()
+    li, e = host(idx2) // n_env, host(idx2) % n_env
+    assert li.min() >= 0 and li.max() <= cap - n_step
+    # logical step li is push li + pushes - cap; a window is cut short by a terminal flag before its last step
+    cut = np.array([flags[l + pushes - cap:l + pushes - cap + n_step - 1, v].any() for l, v in zip(li, e)])
+    assert (e == 0).any() and not cut[e == 0].any(), "no window of the full 32 steps (env 0) was drawn"
+    assert tr.rb.head_sa + li[e == 0].min() <= cap < tr.rb.head_sa + li[e == 0].min() + n_step, "no wrap inside it"
+    assert cut.any(), "no drawn window is cut short by a terminal"
+    folded, iota, idx, key, prio = rl.NStepBatchSampler(n_step, GAMMA, batch, seed=9).sample_fold_prioritized(tr, 3)
+    torch.cuda.synchronize()
+    for name, got, ref in (("idx", idx, idx2), ("key", key, two.key), ("prio", prio, two.priority), ("iota", iota, iota2)):
+        assert torch.equal(got, ref), f"{name}: fused != two launches"
+    rec, rec2 = folded.records.view(torch.int32)[0], folded2.records.view(torch.int32)[0]
+    differing = (rec != rec2).any(1).nonzero().flatten().tolist()
+    assert not differing, f"records {differing[:8]} differ: fused {rec[differing[0]].tolist()} two launches {rec2[differing[0]].tolist()}"
+    assert host(rec[:, 6])[e == 0].max() == 0 and host(rec[:, 6])[cut].min() == 1  # the folded terminal flag says the same
 
 
 # ------------------------------------------------------------------------------------------------------------------ the learner

@@ -1,5 +1,6 @@
-"""Double DQN (profiles/double_dqn.md): event timing of the fold launch alone and of DQNLearner.optimise_ with and without
-double_dqn, each series after a settle phase of untimed calls, as blocks whose median and range are printed.
+"""Double DQN (profiles/double_dqn.md): event timing of the fold launch alone, of DQNLearner.optimise_ with and without
+double_dqn, and (two-layer rows, profiles/fold_stages.md) of rlhip_dqn_sample_fold_f32 -- draw + 3-step window + Double DQN target in
+one launch -- through the C ABI on outputs allocated once, each series after a settle phase of untimed calls, as blocks whose median and range are printed.
 
     python tools/double_dqn_time.py [--tree DIR] [--blocks 7] [--reps 500] [--trace]
 
@@ -31,6 +32,7 @@ import rlhip as rl  # noqa: E402
 assert os.path.abspath(rl.__file__).startswith(tree), rl.__file__
 assert torch.cuda.is_available(), "a timing needs the GPU"
 HAS_FOLD = hasattr(rl, "DoubleTargetFold")
+HAS_SAMPLE_FOLD = hasattr(rl._lib.lib, "rlhip_dqn_sample_fold_f32")
 SETTLE_S = 0.0 if args.trace else 0.3
 if args.trace:
     args.blocks, args.reps = 1, 200
@@ -77,9 +79,27 @@ def update(tr, layers, h, batch, **kw):
     return lambda: L.optimise_(traj)
 
 
+def sample_fold(tr, h, batch, n_step=3):
+    import ctypes as C
+
+    from rlhip._lib import call
+    from rlhip.ops import ptr, stream_ptr
+
+    net = rl.HipApproximator(4, h, 2, seed=1)
+    tn = rl.TargetNetwork(net, sync_freq=100)
+    folded = rl.CircularArraySARTSTraces(capacity=1, n_env=batch, obs_dim=4)
+    idx, iota = (torch.empty(batch, dtype=torch.int64, device="cuda") for _ in range(2))
+
+    def f(_keep=(net, tn, folded, idx, iota)):
+        call("rlhip_dqn_sample_fold_f32", C.byref(tr.rb), batch, n_step, 1, 0.99, 1, 0, h, 2, 0, ptr(net.params), ptr(tn.target),
+             C.byref(folded.rb), ptr(idx), ptr(iota), stream_ptr())
+
+    return f
+
+
 props = torch.cuda.get_device_properties(0)
 print(json.dumps(dict(device=props.name, cus=props.multi_processor_count, torch=torch.__version__, hip=torch.version.hip, tree=tree,
-                      has_fold=HAS_FOLD, blocks=args.blocks, reps=args.reps, settle_s=SETTLE_S, columns="[median, min, max] us")), flush=True)
+                      has_fold=HAS_FOLD, has_sample_fold=HAS_SAMPLE_FOLD, blocks=args.blocks, reps=args.reps, settle_s=SETTLE_S, columns="[median, min, max] us")), flush=True)
 tr = ring()
 for layers, h in ((2, 128), (3, 128), (3, 256)):
     for batch in (512, 4096):
@@ -93,4 +113,6 @@ for layers, h in ((2, 128), (3, 128), (3, 256)):
             row["fold"] = timed(lambda: fold.fold(tr, idx, net, tn.target, tn.target_packed, 0.99))
             row["update_double"] = timed(update(tr, layers, h, batch, double_dqn=True))
             row["update_plain_again"] = timed(update(tr, layers, h, batch))
+        if HAS_SAMPLE_FOLD and layers == 2:
+            row["sample_fold"] = timed(sample_fold(tr, h, batch))
         print(json.dumps(row), flush=True)
