@@ -684,6 +684,60 @@ def test_normlogpdf_huber_td_target(rl):
     assert np.array_equal(host(ops.td_target(dev(qn), dev(r), dev(term), 0.99)), oracle.td_target(qn, r, term, 0.99))
 
 
+def test_normlogpdf_every_output_within_the_budget(rl):
+    """rlhip_normlogpdf_f32 over all of n = 2048 * 256 + 257 outputs (its grid is capped at 2048 blocks of 256: the last 257 are
+    the second trip of the stride loop) against the float64 model of tests/heads_ref.py: one logf, everything else an exact
+    replay.  sigma = 0 (s = 1e-8) and tiny sigma included; the torch cross-check stays"""
+    import heads_ref as H
+    from rlhip import ops
+
+    rng = np.random.default_rng(6)
+    n = 2048 * 256 + 257
+    mu, x = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    sg = rng.uniform(0.1, 3, n).astype(np.float32)
+    sg[::1001] = 0.0
+    sg[1::1001] = 2.5e-3
+    sg[-257:-250] = [0.0, 2.5e-3, 0.1, 1.0, 3.0, 0.0, 2.5e-3]
+    x[2::1001] = mu[2::1001]
+    g = host(ops.normlogpdf(dev(mu), dev(sg), dev(x)))
+    r = H.judge(g, *H.normlogpdf(mu, sg, x), tag=f"normlogpdf n={n}")
+    print(r)
+    ok = sg > 0.05
+    ref = torch.distributions.Normal(torch.tensor(mu[ok]), torch.tensor(sg[ok])).log_prob(torch.tensor(x[ok])).numpy()
+    np.testing.assert_allclose(g[ok], ref, rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("d", [1, 3, 64, 200])
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_diagnormlogpdf_every_output_within_the_budget(rl, n, d):
+    """rlhip_diagnormlogpdf_f32 (no upper limit on d; the head stops at 64) against the identity branch of the head's model, plus
+    its edges: sigma = 0 at d = 1 (v = 1e-16, finite) and d = 3 (prod underflows: +Inf), and a prod in the subnormal range"""
+    import heads_ref as H
+    from rlhip import ops
+
+    rng = np.random.default_rng(100 * d + n)
+    MU, SG, X = (rng.standard_normal((d, n)).astype(np.float32), rng.uniform(0.2, 2, (d, n)).astype(np.float32),
+                 rng.standard_normal((d, n)).astype(np.float32))
+
+    def run(MU, SG, X, tag):
+        gd = host(ops.diagnormlogpdf(dev(MU.T.copy()), dev(SG.T.copy()), dev(X.T.copy())))
+        return gd, H.judge(gd, *H.diagnormlogpdf(MU, SG, X), tag=tag)
+
+    gd, r = run(MU, SG, X, f"diagnormlogpdf d={d} n={n}")
+    assert r["non_finite"] == 0
+    np.testing.assert_allclose(gd, oracle.diagnormlogpdf(MU, SG, X), rtol=1e-5, atol=1e-5)
+    ref = torch.distributions.Normal(torch.tensor(MU), torch.tensor(SG)).log_prob(torch.tensor(X)).sum(0).numpy()
+    np.testing.assert_allclose(gd, ref, rtol=1e-4, atol=1e-5)
+    if d in (1, 3):
+        g0, r0 = run(MU, np.zeros_like(SG), MU + np.float32(1e-8) * X, f"diagnormlogpdf sigma=0 d={d}")
+        assert np.isfinite(g0).all() if d == 1 else (g0 == np.inf).all()
+    if d == 3:
+        M8, S8, X8 = np.tile(MU, (3, 1))[:8], np.full((8, n), 2.5e-3, np.float32), np.tile(X, (3, 1))[:8]
+        S8 += np.float32(1e-4) * rng.random((8, n)).astype(np.float32)
+        g8, r8 = run(M8, S8, M8 + S8 * X8, "diagnormlogpdf subnormal prod")
+        assert np.isfinite(g8).all() and r8["non_finite"] == 0
+
+
 # ----------------------------------------------------------------------------------------- ring
 @pytest.mark.parametrize("n_env,obs_dim,capacity", [(1, 4, 7), (64, 4, 5), (4096, 4, 3), (3, 2, 10)])
 def test_ring_push_sample_gather_bit_exact(rl, n_env, obs_dim, capacity):
