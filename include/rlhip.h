@@ -304,6 +304,49 @@ int32_t rlhip_gaussian_head_sample_f32(const float* mu, const float* raw_sigma, 
 int32_t rlhip_gaussian_head_logp_f32(const float* mu, const float* raw_sigma, const float* action, int64_t d,
                                      int64_t n, int64_t K, float min_sigma, float max_sigma, int32_t squash,
                                      int32_t soft, float* logp_out, rlhip_stream_t stream);
+/* CovGaussianNetwork  RLCore/src/utils/networks.jl:221-381 and the rest of RLCore/src/utils/distributions.jl (csrc/cov_heads.hip).
+ * All arrays f32, column-major: mu (da x n), chol_vec (nv x n) with nv = da (da + 1) / 2 (the output of the Sigma sub-network),
+ * L (da x da x n), actions (da x K x n) -- element (k, j, i) at (i K + j) da + k --, log-probabilities (K x n).  da in 1 ... 16,
+ * K >= 1, n = 0 is a no-op; anything else returns RLHIP_EINVAL.  Noise: draw k + da*j of (seed, env_id_base + i, step) of the Philox
+ * NORMAL stream, as for the heads above.  Order of operations (all f32, no contraction):
+ *   softplusbeta(x) = logf(expf(x / 10.0f) + 1.0f) * 10.0f;  L[i,i] = softplusbeta(v) + 1.0e-5f;  L[i,j] = v (i > j);  0 above;
+ *       1-based vector index of (i, j) = ((2 da - j)(j - 1)) / 2 + i
+ *   sample:  acc = L[i,1] eps[1];  acc = acc + L[i,j] eps[j] (j = 2 ... i);  z[i] = mu[i] + acc
+ *   solve:   t = x[i] - mu[i];  t = t - L[i,j] y[j] (j = 1 ... i - 1 ascending);  y[i] = t / L[i,i]
+ *   logpdf:  ld = 0 + sum_i logf(L[i,i]) ascending;  logdet = 2 ld;  ss = 0 + sum_i y[i] y[i] ascending;
+ *            out = -(((float)da * log2pi + logdet) + ss) / 2       (log2pi = log(2f0 pi), logdetLorU's device method :76)
+ * Only the lower triangle of a dense L is read. */
+/* vec_to_tril(cholesky_vec, da)  networks.jl:359-381 */
+int32_t rlhip_vec_to_tril_f32(const float* chol_vec, int64_t da, int64_t n, float* L_out, rlhip_stream_t stream);
+/* mvnormlogpdf(mu, L, x), the batch form  distributions.jl:46-50, :62-66 (logdetLorU :75-77): out f32 (K x n) */
+int32_t rlhip_mvnormlogpdf_f32(const float* mu, const float* L, const float* x, int64_t da, int64_t K, int64_t n, float* out,
+                               rlhip_stream_t stream);
+/* (model::CovGaussianNetwork)(rng, state; is_sampling = true[, is_return_log_prob = true]) networks.jl:247-272 (K = 1) and
+ * (model)(rng, state, action_samples::Int) :300-312 (K > 1) on the outputs of the mu / Sigma sub-networks, ONE launch: vec_to_tril,
+ * the draws and z = mu + L eps, then mvnormlogpdf(mu, L, z) -- byte for byte what rlhip_vec_to_tril_f32, the product with the same
+ * draws and rlhip_mvnormlogpdf_f32 give.  logp_out (K x n) and L_out (da x da x n) are nullable. */
+int32_t rlhip_cov_gaussian_head_sample_f32(const float* mu, const float* chol_vec, int64_t da, int64_t n, int64_t K,
+                                           uint64_t seed, uint32_t env_id_base, uint32_t step, float* action_out,
+                                           float* logp_out, float* L_out, rlhip_stream_t stream);
+/* (model::CovGaussianNetwork)(state, action)  networks.jl:327-343: vec_to_tril and mvnormlogpdf(mu, L, action) in one launch;
+ * L_out nullable */
+int32_t rlhip_cov_gaussian_head_logp_f32(const float* mu, const float* chol_vec, const float* action, int64_t da, int64_t n,
+                                         int64_t K, float* logp_out, float* L_out, rlhip_stream_t stream);
+/* normkldivergence(mu1, s1, mu2, s2)  distributions.jl:137-139, elementwise over n:
+ *   ((logf(s2) - logf(s1)) + (s1 s1 + (mu1 - mu2)(mu1 - mu2)) / (2 (s2 s2))) - 0.5f */
+int32_t rlhip_normkldivergence_f32(const float* mu1, const float* s1, const float* mu2, const float* s2, int64_t n, float* out,
+                                   rlhip_stream_t stream);
+/* diagnormkldivergence(mu1, s1, mu2, s2)  distributions.jl:117-124: arrays (d x n) column-major, out f32[n] (any d >= 1, as in
+ * diagnormlogpdf).  v = s s;  logdet = sum logf(v2) - sum logf(v1);  trace = sum v1 / v2;  sq = sum ((mu2 - mu1)(mu2 - mu1)) / v2
+ * (every sum from 0, ascending);  out = (((logdet - (float)d) + trace) + sq) / 2 */
+int32_t rlhip_diagnormkldivergence_f32(const float* mu1, const float* s1, const float* mu2, const float* s2, int64_t d,
+                                       int64_t n, float* out, rlhip_stream_t stream);
+/* mvnormkldivergence(mu1, L1, mu2, L2)  distributions.jl:88-109, out f32[n].  The reference's dense inverses and products are
+ * replaced by the equal closed form on triangular solves:  logdet = 2 ld(L2) - 2 ld(L1);  trace = 0 + sum_c sum_{i >= c} w[i,c]^2
+ * with w[:,c] = L2 \ L1[:,c] (columns ascending, rows ascending inside a column, the solve of column c starting at row c);
+ * sq = sum_i (L2 \ (mu2 - mu1))[i]^2;  out = (((logdet - (float)da) + trace) + sq) / 2 */
+int32_t rlhip_mvnormkldivergence_f32(const float* mu1, const float* L1, const float* mu2, const float* L2, int64_t da, int64_t n,
+                                     float* out, rlhip_stream_t stream);
 /* Flux.Losses.huber_loss(q, target; delta) mean-aggregated -> loss_out f32[1]; dq (nullable) = dL/dq */
 int32_t rlhip_huber_f32(const float* q, const float* target, int64_t n, float delta, float* loss_out,
                         float* dq, rlhip_stream_t stream);

@@ -29,7 +29,7 @@ using Random, DomainSets
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, DevValues, HipDuelingApproximator
+    HipPrioritizedTraces, HipStackFrames, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -1224,6 +1224,167 @@ gaussian_logp!(logp::DevBuf{Float32}, mu::DevBuf{Float32}, raw_sigma::DevBuf{Flo
     chk(ccall((:rlhip_gaussian_head_logp_f32, LIB), Int32,
               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float32, Float32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
               mu.ptr, raw_sigma.ptr, action.ptr, d, n, K, min_sigma, max_sigma, squash, soft, logp.ptr, stream()))
+
+# ---- CovGaussianNetwork (RLCore/utils/networks.jl:221-381) and the rest of RLCore/utils/distributions.jl (csrc/cov_heads.hip)
+"vec_to_tril(cholesky_vec, da) (networks.jl:359-381): cholesky_vec (da (da + 1) ÷ 2, n) -> L (da, da, n)"
+vec_to_tril!(L::DevBuf{Float32}, cholesky_vec::DevBuf{Float32}, da, n) =
+    chk(ccall((:rlhip_vec_to_tril_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              cholesky_vec.ptr, da, n, L.ptr, stream()))
+"mvnormlogpdf(μ, L, x), the batch form (distributions.jl:62-66): μ (da, 1, n), L (da, da, n), x (da, K, n) -> out (1, K, n)"
+mvnormlogpdf!(out::DevBuf{Float32}, mu::DevBuf{Float32}, L::DevBuf{Float32}, x::DevBuf{Float32}, da, K, n) =
+    chk(ccall((:rlhip_mvnormlogpdf_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, L.ptr, x.ptr, da, K, n, out.ptr, stream()))
+"(m::CovGaussianNetwork)(rng, s; is_sampling = true, ...) / m(rng, s, K) on the μ / Σ heads' outputs: one launch (networks.jl:247-312);
+`logp` and `L` may be `nothing`"
+cov_gaussian_sample!(action::DevBuf{Float32}, logp, L, mu::DevBuf{Float32}, cholesky_vec::DevBuf{Float32}, da, n, K; seed = 0,
+                     env_id_base = 0, step = 0) =
+    chk(ccall((:rlhip_cov_gaussian_head_sample_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, cholesky_vec.ptr, da, n, K, seed, env_id_base, step, action.ptr, logp === nothing ? C_NULL : logp.ptr,
+              L === nothing ? C_NULL : L.ptr, stream()))
+"(m::CovGaussianNetwork)(s, action): log-probability of given actions (networks.jl:327-343); `L` may be `nothing`"
+cov_gaussian_logp!(logp::DevBuf{Float32}, L, mu::DevBuf{Float32}, cholesky_vec::DevBuf{Float32}, action::DevBuf{Float32}, da, n, K) =
+    chk(ccall((:rlhip_cov_gaussian_head_logp_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, cholesky_vec.ptr, action.ptr, da, n, K, logp.ptr, L === nothing ? C_NULL : L.ptr, stream()))
+normkldivergence!(out::DevBuf{Float32}, mu1::DevBuf{Float32}, s1::DevBuf{Float32}, mu2::DevBuf{Float32}, s2::DevBuf{Float32}, n) =
+    chk(ccall((:rlhip_normkldivergence_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu1.ptr, s1.ptr, mu2.ptr, s2.ptr, n, out.ptr, stream()))
+diagnormkldivergence!(out::DevBuf{Float32}, mu1::DevBuf{Float32}, s1::DevBuf{Float32}, mu2::DevBuf{Float32}, s2::DevBuf{Float32},
+                      d, n) =
+    chk(ccall((:rlhip_diagnormkldivergence_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu1.ptr, s1.ptr, mu2.ptr, s2.ptr, d, n, out.ptr, stream()))
+mvnormkldivergence!(out::DevBuf{Float32}, mu1::DevBuf{Float32}, L1::DevBuf{Float32}, mu2::DevBuf{Float32}, L2::DevBuf{Float32},
+                    da, n) =
+    chk(ccall((:rlhip_mvnormkldivergence_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu1.ptr, L1.ptr, mu2.ptr, L2.ptr, da, n, out.ptr, stream()))
+
+"a Float32 device array with its (column-major) shape: what the μ / Σ sub-networks of a `HipCovGaussianNetwork` return"
+struct DevArray{N}
+    buf::DevBuf{Float32}
+    size::NTuple{N,Int}
+end
+const DevMatrix = DevArray{2}
+const DevArray3 = DevArray{3}
+Base.size(a::DevArray) = a.size
+Base.size(a::DevArray, k) = a.size[k]
+DevArray(size::Vararg{Int,N}) where {N} = DevArray{N}(DevBuf{Float32}(prod(size)), size)
+"reshape shares the buffer (Flux.unsqueeze / dropdims of the reference's call forms)"
+Base.reshape(a::DevArray, size::Vararg{Int,N}) where {N} =
+    prod(size) == prod(a.size) ? DevArray{N}(a.buf, size) : throw(DimensionMismatch("reshape $(a.size) -> $size"))
+
+# the distribution functions of RLCore/utils/distributions.jl on device arrays: methods of the reference's own functions
+function ReinforcementLearningCore.mvnormlogpdf(μ::DevArray3, L::DevArray3, x::DevArray3)     # :62-66
+    da, K, n = size(x)
+    (size(μ) == (da, 1, n) && size(L) == (da, da, n)) || throw(DimensionMismatch("mvnormlogpdf: μ $(size(μ)), L $(size(L)), x $(size(x))"))
+    out = DevArray(1, K, n)
+    mvnormlogpdf!(out.buf, μ.buf, L.buf, x.buf, da, K, n)
+    out
+end
+function ReinforcementLearningCore.mvnormkldivergence(μ1::DevArray3, L1::DevArray3, μ2::DevArray3, L2::DevArray3)   # :105-109
+    da, _, n = size(μ1)
+    (size(μ2) == size(μ1) && size(L1) == size(L2) == (da, da, n)) || throw(DimensionMismatch("mvnormkldivergence"))
+    out = DevArray(1, 1, n)
+    mvnormkldivergence!(out.buf, μ1.buf, L1.buf, μ2.buf, L2.buf, da, n)
+    out
+end
+function ReinforcementLearningCore.diagnormkldivergence(μ1::DevMatrix, σ1::DevMatrix, μ2::DevMatrix, σ2::DevMatrix)   # :117-124
+    d, n = size(μ1)
+    (size(σ1) == size(μ2) == size(σ2) == (d, n)) || throw(DimensionMismatch("diagnormkldivergence"))
+    out = DevArray(1, n)
+    diagnormkldivergence!(out.buf, μ1.buf, σ1.buf, μ2.buf, σ2.buf, d, n)
+    out
+end
+function ReinforcementLearningCore.diagnormkldivergence(μ1::DevArray3, σ1::DevArray3, μ2::DevArray3, σ2::DevArray3)   # :126-129
+    d, _, n = size(μ1)
+    divs = ReinforcementLearningCore.diagnormkldivergence(reshape(μ1, d, n), reshape(σ1, d, n), reshape(μ2, d, n), reshape(σ2, d, n))
+    reshape(divs, 1, 1, n)
+end
+function ReinforcementLearningCore.normkldivergence(μ1::DevArray{N}, σ1::DevArray{N}, μ2::DevArray{N}, σ2::DevArray{N}) where {N}   # :137-139
+    (size(σ1) == size(μ2) == size(σ2) == size(μ1)) || throw(DimensionMismatch("normkldivergence"))
+    out = DevArray(size(μ1)...)
+    normkldivergence!(out.buf, μ1.buf, σ1.buf, μ2.buf, σ2.buf, prod(size(μ1)))
+    out
+end
+
+"""
+    HipCovGaussianNetwork(pre, μ, Σ; seed = 0, env_id_base = 0)
+
+`CovGaussianNetwork(pre, μ, Σ)` (RLCore/utils/networks.jl:221-381) with the head on the device.  `pre`, `μ`, `Σ` are callables on
+`DevArray`s: `μ(x)` returns the means `(da, n)` and `Σ(x)` the Cholesky vectors `(da (da + 1) ÷ 2, n)`.  The call forms are the
+reference's; its `rng` argument is replaced by the shared Philox NORMAL stream `(seed, env_id_base + column, step)` with `step`
+advancing by one per sampling call.
+"""
+mutable struct HipCovGaussianNetwork
+    pre::Any
+    μ::Any
+    Σ::Any
+    seed::UInt64
+    env_id_base::UInt32
+    step::UInt32
+end
+HipCovGaussianNetwork(pre, μ, Σ; seed = 0, env_id_base = 0) =
+    HipCovGaussianNetwork(pre, μ, Σ, UInt64(seed), UInt32(env_id_base), UInt32(0))
+function _cov_heads(m::HipCovGaussianNetwork, state::DevArray)
+    s2 = length(size(state)) == 3 ? reshape(state, size(state, 1), size(state, 3)) : state
+    x = m.pre(s2)
+    μ, v = m.μ(x), m.Σ(x)
+    da, n = size(μ)
+    size(v) == (da * (da + 1) ÷ 2, n) || throw(DimensionMismatch("Σ head: $(size(v)) for da = $da, n = $n"))
+    μ, v, da, n
+end
+function _cov_sample(m::HipCovGaussianNetwork, state::DevArray, K::Int, want_logp::Bool)
+    μ, v, da, n = _cov_heads(m, state)
+    a = DevArray(da, K, n)
+    logp = want_logp ? DevArray(1, K, n) : nothing
+    cov_gaussian_sample!(a.buf, want_logp ? logp.buf : nothing, nothing, μ.buf, v.buf, da, n, K; seed = m.seed,
+                         env_id_base = m.env_id_base, step = m.step)
+    m.step += UInt32(1)
+    a, logp
+end
+"m(state; is_sampling, is_return_log_prob) on a 3-D state (ns, 1, n)  networks.jl:247-272"
+function (m::HipCovGaussianNetwork)(state::DevArray3; is_sampling::Bool = false, is_return_log_prob::Bool = false)
+    if is_sampling
+        a, logp = _cov_sample(m, state, 1, is_return_log_prob)
+        return is_return_log_prob ? (a, logp) : a
+    end
+    μ, v, da, n = _cov_heads(m, state)
+    L = DevArray(da, da, n)
+    vec_to_tril!(L.buf, v.buf, da, n)
+    reshape(μ, da, 1, n), L
+end
+"... on a matrix of states (ns, n): actions, μ and logp as matrices, L stays 3-D  networks.jl:279-289"
+function (m::HipCovGaussianNetwork)(state::DevMatrix; is_sampling::Bool = false, is_return_log_prob::Bool = false)
+    out = m(reshape(state, size(state, 1), 1, size(state, 2)); is_sampling = is_sampling, is_return_log_prob = is_return_log_prob)
+    drop(a::DevArray3) = reshape(a, size(a, 1), size(a, 3))
+    if out isa Tuple && is_sampling
+        drop(out[1]), drop(out[2])
+    elseif out isa Tuple
+        drop(out[1]), out[2]
+    else
+        drop(out)
+    end
+end
+"m(state, action_samples::Int) -> actions (da, K, n), logp (1, K, n)  networks.jl:300-312"
+(m::HipCovGaussianNetwork)(state::DevArray3, action_samples::Int) = _cov_sample(m, state, action_samples, true)
+"m(state, action) -> logp (1, K, n)  networks.jl:327-334"
+function (m::HipCovGaussianNetwork)(state::DevArray3, action::DevArray3)
+    μ, v, da, n = _cov_heads(m, state)
+    (size(action, 1) == da && size(action, 3) == n) || throw(DimensionMismatch("action $(size(action)) for μ ($da, $n)"))
+    K = size(action, 2)
+    logp = DevArray(1, K, n)
+    cov_gaussian_logp!(logp.buf, nothing, μ.buf, v.buf, action.buf, da, n, K)
+    logp
+end
+"2-D states and actions, paired column-wise -> (1, n)  networks.jl:340-343"
+function (m::HipCovGaussianNetwork)(state::DevMatrix, action::DevMatrix)
+    out = m(reshape(state, size(state, 1), 1, size(state, 2)), reshape(action, size(action, 1), 1, size(action, 2)))
+    reshape(out, 1, size(out, 3))
+end
 
 # ---- the same rows on the REFERENCE's types (round 4): what a user of the reference writes keeps working when the values /
 # traces live on the device.  These are methods, not new entry points: each one forwards to a free function above.

@@ -88,8 +88,86 @@ class SoftGaussianNetwork(GaussianNetwork):
         super().__init__(pre, mu, sigma, min_sigma, max_sigma, "tanh", seed, env_id_base)
 
 
+class CovGaussianNetwork:
+    """CovGaussianNetwork(pre, μ, Σ)  RLCore/src/utils/networks.jl:221-381: a Gaussian policy with a full covariance matrix.
+
+    `mu` maps the features to the means (da, n) and `Sigma` to the Cholesky vectors (da (da + 1) / 2, n); `vec_to_tril`, the draw
+    `z = μ + L ε` and `mvnormlogpdf(μ, L, z)` are one launch (csrc/cov_heads.hip).  Call forms, in the reference's shapes:
+      net(state)                  state (ns, n) -> μ (da, n), L (da, da, n);  state (ns, 1, n) -> μ (da, 1, n), L (da, da, n)   :247-289
+      net(state, is_sampling=True[, is_return_log_prob=True])   actions (da, n) [(da, 1, n)] and logp (1, n) [(1, 1, n)]
+      net.sample(state, K)        actions (da, K, n), logp (1, K, n)                                                           :300-312
+      net(state, action)          action (da, n) -> (1, n);  action (da, K, n) -> (1, K, n)                                    :327-343
+    `step` advances by one per sampling call."""
+
+    def __init__(self, pre=None, mu=None, Sigma=None, seed=0, env_id_base=0):
+        self.pre = pre if pre is not None else (lambda x: x)
+        self.mu, self.Sigma = mu, Sigma
+        self.seed, self.env_id_base, self.step = int(seed), int(env_id_base), 0
+
+    def heads(self, state):
+        """-> μ (da, n), cholesky_vec (nv, n); a 3-D state (ns, 1, n) is the 2-D one with a unit middle axis (:280)"""
+        if state.dim() == 3:
+            state = state[:, 0, :]
+        x = self.pre(state)
+        mu, vec = self.mu(x), self.Sigma(x)
+        da = mu.shape[0]
+        if mu.dim() != 2 or vec.dim() != 2 or vec.shape[0] != da * (da + 1) // 2 or vec.shape[1] != mu.shape[1]:
+            raise ValueError(f"CovGaussianNetwork: μ {tuple(mu.shape)} needs a Σ head of shape ({da * (da + 1) // 2}, {mu.shape[1]}), "
+                             f"got {tuple(vec.shape)}")
+        return mu, vec
+
+    def __call__(self, state, action=None, is_sampling=False, is_return_log_prob=False):
+        if action is not None:
+            return self.logp(state, action)
+        three = state.dim() == 3
+        mu, vec = self.heads(state)
+        if not is_sampling:
+            da, n = mu.shape
+            vec_s = _cm(vec)
+            L = torch.empty((n, da, da), dtype=torch.float32, device=mu.device)
+            call("rlhip_vec_to_tril_f32", ptr(vec_s), da, n, ptr(L), stream_ptr())
+            return (mu.unsqueeze(1) if three else mu), L.permute(2, 1, 0)  # :270, :285
+        a, lp = self._sample(mu, vec, 1, is_return_log_prob)
+        a = a.permute(2, 1, 0) if three else a[:, 0, :].t()
+        if not is_return_log_prob:
+            return a
+        return a, (lp.t().unsqueeze(0) if three else lp.reshape(1, -1))
+
+    def sample(self, state, action_samples):
+        """(model)(state::(ns, 1, n), action_samples::Int) -> actions (da, K, n), logp (1, K, n)  :300-312"""
+        mu, vec = self.heads(state)
+        a, lp = self._sample(mu, vec, int(action_samples), True)
+        return a.permute(2, 1, 0), lp.t().unsqueeze(0)
+
+    def logp(self, state, action):
+        """(model)(state, action) -> logp (1, n) or (1, K, n)  :327-343"""
+        three = action.dim() == 3
+        mu, vec = self.heads(state)
+        da, n = mu.shape
+        if action.shape[0] != da or action.shape[-1] != n:
+            raise ValueError(f"CovGaussianNetwork: actions {tuple(action.shape)} for μ {tuple(mu.shape)}")
+        act = action.permute(2, 1, 0).contiguous() if three else action.t().contiguous().reshape(n, 1, da)
+        K = act.shape[1]
+        out = torch.empty((n, K), dtype=torch.float32, device=mu.device)
+        mu_s, vec_s = _cm(mu), _cm(vec)  # keep the transposed copies alive across the (asynchronous) call
+        call("rlhip_cov_gaussian_head_logp_f32", ptr(mu_s), ptr(vec_s), ptr(act), da, n, K, ptr(out), None, stream_ptr())
+        return out.t().unsqueeze(0) if three else out.reshape(1, n)
+
+    def _sample(self, mu, vec, K, want_logp, want_L=False):
+        """-> actions (n, K, da), logp (n, K) or None[, L (n, da, da)]: the storages of the reference's arrays"""
+        da, n = mu.shape
+        act = torch.empty((n, K, da), dtype=torch.float32, device=mu.device)
+        lp = torch.empty((n, K), dtype=torch.float32, device=mu.device) if want_logp else None
+        L = torch.empty((n, da, da), dtype=torch.float32, device=mu.device) if want_L else None
+        mu_s, vec_s = _cm(mu), _cm(vec)  # keep the transposed copies alive across the (asynchronous) call
+        call("rlhip_cov_gaussian_head_sample_f32", ptr(mu_s), ptr(vec_s), da, n, K, self.seed, self.env_id_base, self.step,
+             ptr(act), ptr(lp), ptr(L), stream_ptr())
+        self.step += 1
+        return (act, lp, L) if want_L else (act, lp)
+
+
 class CategoricalNetwork:
-    """CategoricalNetwork(model)  RLCore/src/utils/networks.jl:405-432 (+ masked methods :459-472).
+    """CategoricalNetwork(model) RLCore/src/utils/networks.jl:405-432 (+ masked methods :459-472).
 
     `model` maps a state batch to logits shaped (na, n).  `(net)(state; is_sampling, is_return_log_prob)` returns the
     logits, or a one-hot `z` (na, n) drawn with the Gumbel-max trick (`sample_categorical` :425-432, one launch:

@@ -196,6 +196,62 @@ def diagnormlogpdf(mu, sigma, x):
     return out
 
 
+def vec_to_tril(chol_vec, da):
+    """vec_to_tril(cholesky_vec, da)  RLCore/src/utils/networks.jl:359-381.  chol_vec: storage of a Julia (nv, n) matrix, torch shape
+    (n, nv) with nv = da (da + 1) / 2 -> storage of the Julia (da, da, n) array L: torch shape (n, da, da) indexed [state, column, row]."""
+    n, nv = chol_vec.shape
+    if nv != da * (da + 1) // 2:
+        raise _lib.RLHipArgumentError(f"a Cholesky vector for da = {da} has {da * (da + 1) // 2} elements, got {nv}")
+    out = torch.empty((n, da, da), dtype=torch.float32, device=chol_vec.device)
+    call("rlhip_vec_to_tril_f32", ptr(chol_vec), da, n, ptr(out), stream_ptr())
+    return out
+
+
+def mvnormlogpdf(mu, L, x):
+    """mvnormlogpdf(mu, L, x), the batch form  RLCore/src/utils/distributions.jl:46-66.  Storages of the Julia arrays: mu (n, da)
+    [Julia (da, 1, n)], L (n, da, da) [Julia (da, da, n)], x (n, K, da) [Julia (da, K, n)] -> (n, K) [Julia (1, K, n)]; x (n, da) is
+    K = 1 and gives (n,)."""
+    n, da = mu.shape
+    flat = x.dim() == 2
+    K = 1 if flat else x.shape[1]
+    if tuple(L.shape) != (n, da, da) or tuple(x.shape) != ((n, da) if flat else (n, K, da)):
+        raise _lib.RLHipArgumentError(f"mvnormlogpdf: mu {tuple(mu.shape)}, L {tuple(L.shape)}, x {tuple(x.shape)} do not agree")
+    out = torch.empty((n,) if flat else (n, K), dtype=torch.float32, device=mu.device)
+    call("rlhip_mvnormlogpdf_f32", ptr(mu), ptr(L), ptr(x), da, K, n, ptr(out), stream_ptr())
+    return out
+
+
+def normkldivergence(mu1, sigma1, mu2, sigma2):
+    """normkldivergence(mu1, sigma1, mu2, sigma2) elementwise  RLCore/src/utils/distributions.jl:137-139"""
+    if not (mu1.shape == sigma1.shape == mu2.shape == sigma2.shape):
+        raise _lib.RLHipArgumentError("normkldivergence: the four arguments must have one shape")
+    out = torch.empty_like(mu1)
+    call("rlhip_normkldivergence_f32", ptr(mu1), ptr(sigma1), ptr(mu2), ptr(sigma2), mu1.numel(), ptr(out), stream_ptr())
+    return out
+
+
+def diagnormkldivergence(mu1, sigma1, mu2, sigma2):
+    """diagnormkldivergence  RLCore/src/utils/distributions.jl:117-129.  arrays are storages of Julia (d, n) matrices: torch shape
+    (n, d) -> (n,)."""
+    if not (mu1.dim() == 2 and mu1.shape == sigma1.shape == mu2.shape == sigma2.shape):
+        raise _lib.RLHipArgumentError("diagnormkldivergence: the four arguments must be (n, d) tensors of one shape")
+    n, d = mu1.shape
+    out = torch.empty(n, dtype=torch.float32, device=mu1.device)
+    call("rlhip_diagnormkldivergence_f32", ptr(mu1), ptr(sigma1), ptr(mu2), ptr(sigma2), d, n, ptr(out), stream_ptr())
+    return out
+
+
+def mvnormkldivergence(mu1, L1, mu2, L2):
+    """mvnormkldivergence(mu1, L1, mu2, L2), the batch form  RLCore/src/utils/distributions.jl:88-109.  mu (n, da), L (n, da, da) as in
+    `mvnormlogpdf` -> (n,)."""
+    n, da = mu1.shape
+    if mu2.shape != mu1.shape or tuple(L1.shape) != (n, da, da) or tuple(L2.shape) != (n, da, da):
+        raise _lib.RLHipArgumentError("mvnormkldivergence: mu (n, da) and L (n, da, da) do not agree")
+    out = torch.empty(n, dtype=torch.float32, device=mu1.device)
+    call("rlhip_mvnormkldivergence_f32", ptr(mu1), ptr(L1), ptr(mu2), ptr(L2), da, n, ptr(out), stream_ptr())
+    return out
+
+
 def huber_loss(q, target, delta=1.0, with_grad=True):
     loss = torch.empty(1, dtype=torch.float32, device=q.device)
     dq = torch.empty_like(q) if with_grad else None
