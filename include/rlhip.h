@@ -347,6 +347,50 @@ int32_t rlhip_diagnormkldivergence_f32(const float* mu1, const float* s1, const 
  * sq = sum_i (L2 \ (mu2 - mu1))[i]^2;  out = (((logdet - (float)da) + trace) + sq) / 2 */
 int32_t rlhip_mvnormkldivergence_f32(const float* mu1, const float* L1, const float* mu2, const float* L2, int64_t da, int64_t n,
                                      float* out, rlhip_stream_t stream);
+/* The pullbacks of the functions above (csrc/cov_heads_grad.hip): the reference introduces them as "GPU automatic differentiable"
+ * versions and its users (MPO) differentiate through every one.  A cotangent has the shape of the forward output, a gradient the
+ * shape of the forward input; every output pointer is nullable and its work is skipped; inputs must not be NULL; da in 1 ... 16 for
+ * every entry, K >= 1, n = 0 is a no-op; anything else returns RLHIP_EINVAL.  All f32, no contraction, no atomics; the sums over the
+ * K samples of a state run in ascending k, sequentially, in one lane, so a result does not depend on the launch geometry.
+ *
+ * Pullback of mvnormlogpdf(mu, L, x)  distributions.jl:46-66; dlogp (K x n).  Per state, k = 1 ... K ascending:
+ *   y = L \ (x_k - mu)     the forward solve above
+ *   u = L^T \ y            columns c = da ... 1: u[c] = t[c] / L[c,c]; then t[r] = t[r] - L[c,r] u[c] for r < c
+ *   gu[r] = g_k u[r];  dx_k[r] = -gu[r];  dmu[r] = 0 + sum_k gu_k[r];  S[r,c] = 0 + sum_k gu_k[r] y_k[c] (r >= c);  gs = 0 + sum_k g_k
+ *   dL[r,c] = S[r,c] (r > c);  dL[c,c] = S[c,c] - gs / L[c,c];  dL_out is dense (da x da x n) with +0 above the diagonal */
+int32_t rlhip_mvnormlogpdf_bwd_f32(const float* mu, const float* L, const float* x, const float* dlogp, int64_t da, int64_t K,
+                                   int64_t n, float* dmu_out, float* dL_out, float* dx_out, rlhip_stream_t stream);
+/* Pullback of vec_to_tril(cholesky_vec, da)  networks.jl:359-381: dvec = dL[r,c] below the diagonal and
+ * dL[c,c] * (1.0f / (1.0f + expf(-(v / 10.0f)))) on it (the derivative of softplusbeta in the form that stays finite where
+ * expf(v / 10) overflows).  Only the lower triangle of dL is read. */
+int32_t rlhip_vec_to_tril_bwd_f32(const float* chol_vec, const float* dL, int64_t da, int64_t n, float* dvec_out,
+                                  rlhip_stream_t stream);
+/* Pullback of (model::CovGaussianNetwork)(state, action)  networks.jl:327-343 onto the outputs of the mu / Sigma sub-networks, ONE
+ * launch: byte for byte what rlhip_vec_to_tril_f32 -> rlhip_mvnormlogpdf_bwd_f32 -> rlhip_vec_to_tril_bwd_f32 give, without a dense L
+ * or dL in memory.  The sampling calls need no pullback of their own: the reference draws z under ignore_derivatives
+ * (networks.jl:255, :306), so the gradient of their log-probability is this call with action = the sampled z. */
+int32_t rlhip_cov_gaussian_head_logp_bwd_f32(const float* mu, const float* chol_vec, const float* action, const float* dlogp,
+                                             int64_t da, int64_t n, int64_t K, float* dmu_out, float* dvec_out,
+                                             rlhip_stream_t stream);
+/* Pullback of mvnormkldivergence(mu1, L1, mu2, L2)  distributions.jl:88-109; dout f32[n] = g.  Per state:
+ *   m = L2 \ (mu2 - mu1);  q = L2^T \ m;  dmu2[r] = g q[r];  dmu1[r] = -(g q[r]);  W[r,j] = q[r] m[j] (r >= j)
+ *   for c = 1 ... da:  a = L2 \ L1[:,c] from row c (the rows above are +0);  p = L2^T \ a (all rows);
+ *       dL1[r,c] = g p[r] (r > c);  dL1[c,c] = g (p[c] - 1.0f / L1[c,c]);  W[r,j] = W[r,j] + p[r] a[j] for c <= j <= r
+ *   dL2[r,j] = g (-W[r,j]) (r > j);  dL2[j,j] = g (1.0f / L2[j,j] - W[j,j]);  dL1, dL2 dense with +0 above the diagonal */
+int32_t rlhip_mvnormkldivergence_bwd_f32(const float* mu1, const float* L1, const float* mu2, const float* L2, const float* dout,
+                                         int64_t da, int64_t n, float* dmu1_out, float* dL1_out, float* dmu2_out, float* dL2_out,
+                                         rlhip_stream_t stream);
+/* Pullback of diagnormkldivergence(mu1, s1, mu2, s2)  distributions.jl:117-124; dout f32[n], g the column's.  Per component, with
+ * a = s1, b = s2, dm = mu2 - mu1, v1 = a a, v2 = b b, w = dm / v2:
+ *   dmu2 = g w;  dmu1 = -(g w);  ds1 = g (a / v2 - 1.0f / a);  ds2 = g (1.0f / b - (v1 + dm dm) / (v2 b)) */
+int32_t rlhip_diagnormkldivergence_bwd_f32(const float* mu1, const float* s1, const float* mu2, const float* s2, const float* dout,
+                                           int64_t d, int64_t n, float* dmu1_out, float* ds1_out, float* dmu2_out, float* ds2_out,
+                                           rlhip_stream_t stream);
+/* Pullback of normkldivergence(mu1, s1, mu2, s2)  distributions.jl:137-139, elementwise; dout f32[n].  dm = mu1 - mu2, v2 = b b,
+ * w = dm / v2:  dmu1 = g w;  dmu2 = -(g w);  ds1 = g (a / v2 - 1.0f / a);  ds2 = g (1.0f / b - (a a + dm dm) / (v2 b)) */
+int32_t rlhip_normkldivergence_bwd_f32(const float* mu1, const float* s1, const float* mu2, const float* s2, const float* dout,
+                                       int64_t n, float* dmu1_out, float* ds1_out, float* dmu2_out, float* ds2_out,
+                                       rlhip_stream_t stream);
 /* Flux.Losses.huber_loss(q, target; delta) mean-aggregated -> loss_out f32[1]; dq (nullable) = dL/dq */
 int32_t rlhip_huber_f32(const float* q, const float* target, int64_t n, float delta, float* loss_out,
                         float* dq, rlhip_stream_t stream);

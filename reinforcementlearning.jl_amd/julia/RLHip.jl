@@ -26,6 +26,8 @@ import ReinforcementLearningCore: _run, check!, forward, target, model, PreExper
 # name is not exported from here, so `using RLHip` next to StatsBase / ReinforcementLearning cannot produce two `sample`s (ADVICE r4)
 import ReinforcementLearningCore: sample
 using Random, DomainSets
+import ChainRulesCore
+using ChainRulesCore: NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
@@ -1375,7 +1377,12 @@ end
 function (m::HipCovGaussianNetwork)(state::DevArray3, action::DevArray3)
     μ, v, da, n = _cov_heads(m, state)
     (size(action, 1) == da && size(action, 3) == n) || throw(DimensionMismatch("action $(size(action)) for μ ($da, $n)"))
-    K = size(action, 2)
+    cov_gaussian_logp(μ, v, action)
+end
+"mvnormlogpdf(μ, vec_to_tril(v, da), action) in one launch: μ (da, n), v (da (da + 1) ÷ 2, n), action (da, K, n) -> (1, K, n).  The
+(state, action) call above is `pre`, `μ`, `Σ` followed by this function, and this function carries the `rrule` (below)."
+function cov_gaussian_logp(μ::DevMatrix, v::DevMatrix, action::DevArray3)
+    da, K, n = size(action)
     logp = DevArray(1, K, n)
     cov_gaussian_logp!(logp.buf, nothing, μ.buf, v.buf, action.buf, da, n, K)
     logp
@@ -1384,6 +1391,118 @@ end
 function (m::HipCovGaussianNetwork)(state::DevMatrix, action::DevMatrix)
     out = m(reshape(state, size(state, 1), 1, size(state, 2)), reshape(action, size(action, 1), 1, size(action, 2)))
     reshape(out, 1, size(out, 3))
+end
+
+# ---- the pullbacks of the distribution functions and of the head (csrc/cov_heads_grad.hip).  The reference introduces every one of these
+# functions as a "GPU automatic differentiable version" (distributions.jl) and differentiates through them (MPO); on `DevArray`s the
+# derivative is a kernel, handed to the AD through ChainRulesCore.  Like the rest of this module none of this has been executed: the
+# `ccall`s are checked against include/rlhip.h by tests/test_julia_glue_signatures.py, the kernels behind them by the Python suite.
+_ptr(b) = b === nothing ? C_NULL : b.ptr
+"pullback of mvnormlogpdf(μ, L, x): dlogp (1, K, n) -> dμ, dL (dense, zeros above the diagonal), dx; each may be `nothing`"
+mvnormlogpdf_bwd!(dmu, dL, dx, mu::DevBuf{Float32}, L::DevBuf{Float32}, x::DevBuf{Float32}, dlogp::DevBuf{Float32}, da, K, n) =
+    chk(ccall((:rlhip_mvnormlogpdf_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, L.ptr, x.ptr, dlogp.ptr, da, K, n, _ptr(dmu), _ptr(dL), _ptr(dx), stream()))
+"pullback of vec_to_tril(cholesky_vec, da): only the lower triangle of dL is read"
+vec_to_tril_bwd!(dvec::DevBuf{Float32}, cholesky_vec::DevBuf{Float32}, dL::DevBuf{Float32}, da, n) =
+    chk(ccall((:rlhip_vec_to_tril_bwd_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              cholesky_vec.ptr, dL.ptr, da, n, dvec.ptr, stream()))
+"pullback of (m::CovGaussianNetwork)(s, action) onto the μ / Σ heads' outputs, one launch; the sampling calls' log-probability is
+pulled back by the same call with `action` = the sampled z (the reference draws z under `ignore_derivatives`, networks.jl:255, :306)"
+cov_gaussian_logp_bwd!(dmu, dvec, mu::DevBuf{Float32}, cholesky_vec::DevBuf{Float32}, action::DevBuf{Float32},
+                       dlogp::DevBuf{Float32}, da, n, K) =
+    chk(ccall((:rlhip_cov_gaussian_head_logp_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, cholesky_vec.ptr, action.ptr, dlogp.ptr, da, n, K, _ptr(dmu), _ptr(dvec), stream()))
+mvnormkldivergence_bwd!(dmu1, dL1, dmu2, dL2, mu1::DevBuf{Float32}, L1::DevBuf{Float32}, mu2::DevBuf{Float32}, L2::DevBuf{Float32},
+                        dout::DevBuf{Float32}, da, n) =
+    chk(ccall((:rlhip_mvnormkldivergence_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              mu1.ptr, L1.ptr, mu2.ptr, L2.ptr, dout.ptr, da, n, _ptr(dmu1), _ptr(dL1), _ptr(dmu2), _ptr(dL2), stream()))
+diagnormkldivergence_bwd!(dmu1, ds1, dmu2, ds2, mu1::DevBuf{Float32}, s1::DevBuf{Float32}, mu2::DevBuf{Float32}, s2::DevBuf{Float32},
+                          dout::DevBuf{Float32}, d, n) =
+    chk(ccall((:rlhip_diagnormkldivergence_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              mu1.ptr, s1.ptr, mu2.ptr, s2.ptr, dout.ptr, d, n, _ptr(dmu1), _ptr(ds1), _ptr(dmu2), _ptr(ds2), stream()))
+normkldivergence_bwd!(dmu1, ds1, dmu2, ds2, mu1::DevBuf{Float32}, s1::DevBuf{Float32}, mu2::DevBuf{Float32}, s2::DevBuf{Float32},
+                      dout::DevBuf{Float32}, n) =
+    chk(ccall((:rlhip_normkldivergence_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu1.ptr, s1.ptr, mu2.ptr, s2.ptr, dout.ptr, n, _ptr(dmu1), _ptr(ds1), _ptr(dmu2), _ptr(ds2), stream()))
+
+"vec_to_tril(cholesky_vec, da) on a device matrix (networks.jl:378-381) -> L (da, da, n)"
+function ReinforcementLearningCore.vec_to_tril(v::DevMatrix, da::Integer)
+    n = size(v, 2)
+    size(v, 1) == da * (da + 1) ÷ 2 || throw(DimensionMismatch("vec_to_tril: $(size(v)) for da = $da"))
+    L = DevArray(da, da, n)
+    vec_to_tril!(L.buf, v.buf, da, n)
+    L
+end
+_like(a::DevArray) = DevArray(size(a)...)
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.vec_to_tril), v::DevMatrix, da::Integer)
+    L = ReinforcementLearningCore.vec_to_tril(v, da)
+    function vec_to_tril_pullback(dL)
+        dv = _like(v)
+        vec_to_tril_bwd!(dv.buf, v.buf, unthunk(dL).buf, da, size(v, 2))
+        NoTangent(), dv, NoTangent()
+    end
+    L, vec_to_tril_pullback
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.mvnormlogpdf), μ::DevArray3, L::DevArray3, x::DevArray3)
+    out = ReinforcementLearningCore.mvnormlogpdf(μ, L, x)
+    da, K, n = size(x)
+    function mvnormlogpdf_pullback(dlogp)
+        dμ, dL, dx = _like(μ), _like(L), _like(x)
+        mvnormlogpdf_bwd!(dμ.buf, dL.buf, dx.buf, μ.buf, L.buf, x.buf, unthunk(dlogp).buf, da, K, n)
+        NoTangent(), dμ, dL, dx
+    end
+    out, mvnormlogpdf_pullback
+end
+"the head: (m::HipCovGaussianNetwork)(state, action) is `pre`, `μ`, `Σ` and then `cov_gaussian_logp`, so this rule is its pullback onto
+the sub-networks' outputs; the actions get no tangent from the fused launch (use mvnormlogpdf(μ, vec_to_tril(v, da), action) for one)"
+function ChainRulesCore.rrule(::typeof(cov_gaussian_logp), μ::DevMatrix, v::DevMatrix, action::DevArray3)
+    out = cov_gaussian_logp(μ, v, action)
+    da, K, n = size(action)
+    function cov_gaussian_logp_pullback(dlogp)
+        dμ, dv = _like(μ), _like(v)
+        cov_gaussian_logp_bwd!(dμ.buf, dv.buf, μ.buf, v.buf, action.buf, unthunk(dlogp).buf, da, n, K)
+        NoTangent(), dμ, dv, NoTangent()
+    end
+    out, cov_gaussian_logp_pullback
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.mvnormkldivergence), μ1::DevArray3, L1::DevArray3, μ2::DevArray3,
+                              L2::DevArray3)
+    out = ReinforcementLearningCore.mvnormkldivergence(μ1, L1, μ2, L2)
+    da, _, n = size(μ1)
+    function mvnormkldivergence_pullback(dout)
+        dμ1, dL1, dμ2, dL2 = _like(μ1), _like(L1), _like(μ2), _like(L2)
+        mvnormkldivergence_bwd!(dμ1.buf, dL1.buf, dμ2.buf, dL2.buf, μ1.buf, L1.buf, μ2.buf, L2.buf, unthunk(dout).buf, da, n)
+        NoTangent(), dμ1, dL1, dμ2, dL2
+    end
+    out, mvnormkldivergence_pullback
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.diagnormkldivergence), μ1::DevMatrix, σ1::DevMatrix, μ2::DevMatrix,
+                              σ2::DevMatrix)
+    out = ReinforcementLearningCore.diagnormkldivergence(μ1, σ1, μ2, σ2)
+    d, n = size(μ1)
+    function diagnormkldivergence_pullback(dout)
+        dμ1, dσ1, dμ2, dσ2 = _like(μ1), _like(σ1), _like(μ2), _like(σ2)
+        diagnormkldivergence_bwd!(dμ1.buf, dσ1.buf, dμ2.buf, dσ2.buf, μ1.buf, σ1.buf, μ2.buf, σ2.buf, unthunk(dout).buf, d, n)
+        NoTangent(), dμ1, dσ1, dμ2, dσ2
+    end
+    out, diagnormkldivergence_pullback
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.normkldivergence), μ1::DevArray{N}, σ1::DevArray{N}, μ2::DevArray{N},
+                              σ2::DevArray{N}) where {N}
+    out = ReinforcementLearningCore.normkldivergence(μ1, σ1, μ2, σ2)
+    function normkldivergence_pullback(dout)
+        dμ1, dσ1, dμ2, dσ2 = _like(μ1), _like(σ1), _like(μ2), _like(σ2)
+        normkldivergence_bwd!(dμ1.buf, dσ1.buf, dμ2.buf, dσ2.buf, μ1.buf, σ1.buf, μ2.buf, σ2.buf, unthunk(dout).buf, prod(size(μ1)))
+        NoTangent(), dμ1, dσ1, dμ2, dσ2
+    end
+    out, normkldivergence_pullback
 end
 
 # ---- the same rows on the REFERENCE's types (round 4): what a user of the reference writes keeps working when the values /

@@ -8,8 +8,9 @@ column-major sense, i.e. torch tensors of shape (batch, features) whose memory i
 shared Philox NORMAL stream: (seed, env_id_base + column, step) with `step` advancing by one per sampling call."""
 import torch
 
+from . import ops
 from ._lib import call
-from .ops import ptr, stream_ptr
+from .ops import _wants_grad, ptr, stream_ptr
 
 
 def _cm(x):
@@ -97,7 +98,12 @@ class CovGaussianNetwork:
       net(state, is_sampling=True[, is_return_log_prob=True])   actions (da, n) [(da, 1, n)] and logp (1, n) [(1, 1, n)]
       net.sample(state, K)        actions (da, K, n), logp (1, K, n)                                                           :300-312
       net(state, action)          action (da, n) -> (1, n);  action (da, K, n) -> (1, K, n)                                    :327-343
-    `step` advances by one per sampling call."""
+    `step` advances by one per sampling call.
+
+    With torch modules as `mu` / `Sigma` the head is trainable: while autograd is recording and a head output requires a gradient, the
+    log-probabilities of `net(state, action)` and of the sampling calls are pulled back in one launch (rlhip/grad.py,
+    csrc/cov_heads_grad.hip), `net(state)`'s L through `vec_to_tril`'s pullback; the values are bit-identical to the plain path and
+    the sampled actions carry no gradient, as in the reference (`ignore_derivatives`)."""
 
     def __init__(self, pre=None, mu=None, Sigma=None, seed=0, env_id_base=0):
         self.pre = pre if pre is not None else (lambda x: x)
@@ -123,9 +129,7 @@ class CovGaussianNetwork:
         mu, vec = self.heads(state)
         if not is_sampling:
             da, n = mu.shape
-            vec_s = _cm(vec)
-            L = torch.empty((n, da, da), dtype=torch.float32, device=mu.device)
-            call("rlhip_vec_to_tril_f32", ptr(vec_s), da, n, ptr(L), stream_ptr())
+            L = ops.vec_to_tril(_cm(vec), da)
             return (mu.unsqueeze(1) if three else mu), L.permute(2, 1, 0)  # :270, :285
         a, lp = self._sample(mu, vec, 1, is_return_log_prob)
         a = a.permute(2, 1, 0) if three else a[:, 0, :].t()
@@ -147,23 +151,49 @@ class CovGaussianNetwork:
         if action.shape[0] != da or action.shape[-1] != n:
             raise ValueError(f"CovGaussianNetwork: actions {tuple(action.shape)} for μ {tuple(mu.shape)}")
         act = action.permute(2, 1, 0).contiguous() if three else action.t().contiguous().reshape(n, 1, da)
-        K = act.shape[1]
-        out = torch.empty((n, K), dtype=torch.float32, device=mu.device)
         mu_s, vec_s = _cm(mu), _cm(vec)  # keep the transposed copies alive across the (asynchronous) call
-        call("rlhip_cov_gaussian_head_logp_f32", ptr(mu_s), ptr(vec_s), ptr(act), da, n, K, ptr(out), None, stream_ptr())
+        if _wants_grad(act):  # a gradient for the actions too: the composition, byte for byte the fused call
+            out = ops.mvnormlogpdf(mu_s, ops.vec_to_tril(vec_s, da), act)
+        elif _wants_grad(mu_s, vec_s):
+            from . import grad
+
+            out = grad.CovHeadLogp.apply(mu_s, vec_s, act)
+        else:
+            out = cov_logp(mu_s, vec_s, act)
         return out.t().unsqueeze(0) if three else out.reshape(1, n)
 
     def _sample(self, mu, vec, K, want_logp, want_L=False):
         """-> actions (n, K, da), logp (n, K) or None[, L (n, da, da)]: the storages of the reference's arrays"""
-        da, n = mu.shape
-        act = torch.empty((n, K, da), dtype=torch.float32, device=mu.device)
-        lp = torch.empty((n, K), dtype=torch.float32, device=mu.device) if want_logp else None
-        L = torch.empty((n, da, da), dtype=torch.float32, device=mu.device) if want_L else None
         mu_s, vec_s = _cm(mu), _cm(vec)  # keep the transposed copies alive across the (asynchronous) call
-        call("rlhip_cov_gaussian_head_sample_f32", ptr(mu_s), ptr(vec_s), da, n, K, self.seed, self.env_id_base, self.step,
-             ptr(act), ptr(lp), ptr(L), stream_ptr())
+        if want_logp and not want_L and _wants_grad(mu_s, vec_s):
+            from . import grad
+
+            act, lp = grad.CovHeadSample.apply(mu_s, vec_s, K, self.seed, self.env_id_base, self.step)
+            L = None
+        else:
+            act, lp, L = cov_sample(mu_s, vec_s, K, self.seed, self.env_id_base, self.step, want_logp, want_L)
         self.step += 1
         return (act, lp, L) if want_L else (act, lp)
+
+
+def cov_logp(mu_s, vec_s, act):
+    """the (state, action) launch on storages: mu_s (n, da), vec_s (n, nv), act (n, K, da) -> logp (n, K); no autograd"""
+    n, da = mu_s.shape
+    K = act.shape[1]
+    out = torch.empty((n, K), dtype=torch.float32, device=mu_s.device)
+    call("rlhip_cov_gaussian_head_logp_f32", ptr(mu_s), ptr(vec_s), ptr(act), da, n, K, ptr(out), None, stream_ptr())
+    return out
+
+
+def cov_sample(mu_s, vec_s, K, seed, env_id_base, step, want_logp, want_L):
+    """the sampling launch on storages -> actions (n, K, da), logp (n, K) or None, L (n, da, da) or None; no autograd"""
+    n, da = mu_s.shape
+    act = torch.empty((n, K, da), dtype=torch.float32, device=mu_s.device)
+    lp = torch.empty((n, K), dtype=torch.float32, device=mu_s.device) if want_logp else None
+    L = torch.empty((n, da, da), dtype=torch.float32, device=mu_s.device) if want_L else None
+    call("rlhip_cov_gaussian_head_sample_f32", ptr(mu_s), ptr(vec_s), da, n, K, seed, env_id_base, step, ptr(act), ptr(lp), ptr(L),
+         stream_ptr())
+    return act, lp, L
 
 
 class CategoricalNetwork:

@@ -196,9 +196,18 @@ def diagnormlogpdf(mu, sigma, x):
     return out
 
 
+def _wants_grad(*tensors):
+    """autograd is recording and an input asks for a gradient: the call goes through rlhip/grad.py (same kernels, same values)"""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def vec_to_tril(chol_vec, da):
     """vec_to_tril(cholesky_vec, da)  RLCore/src/utils/networks.jl:359-381.  chol_vec: storage of a Julia (nv, n) matrix, torch shape
     (n, nv) with nv = da (da + 1) / 2 -> storage of the Julia (da, da, n) array L: torch shape (n, da, da) indexed [state, column, row]."""
+    if _wants_grad(chol_vec):
+        from . import grad
+
+        return grad.VecToTril.apply(chol_vec, da)
     n, nv = chol_vec.shape
     if nv != da * (da + 1) // 2:
         raise _lib.RLHipArgumentError(f"a Cholesky vector for da = {da} has {da * (da + 1) // 2} elements, got {nv}")
@@ -211,6 +220,10 @@ def mvnormlogpdf(mu, L, x):
     """mvnormlogpdf(mu, L, x), the batch form  RLCore/src/utils/distributions.jl:46-66.  Storages of the Julia arrays: mu (n, da)
     [Julia (da, 1, n)], L (n, da, da) [Julia (da, da, n)], x (n, K, da) [Julia (da, K, n)] -> (n, K) [Julia (1, K, n)]; x (n, da) is
     K = 1 and gives (n,)."""
+    if _wants_grad(mu, L, x):
+        from . import grad
+
+        return grad.MvNormLogPdf.apply(mu, L, x)
     n, da = mu.shape
     flat = x.dim() == 2
     K = 1 if flat else x.shape[1]
@@ -223,6 +236,10 @@ def mvnormlogpdf(mu, L, x):
 
 def normkldivergence(mu1, sigma1, mu2, sigma2):
     """normkldivergence(mu1, sigma1, mu2, sigma2) elementwise  RLCore/src/utils/distributions.jl:137-139"""
+    if _wants_grad(mu1, sigma1, mu2, sigma2):
+        from . import grad
+
+        return grad.NormKL.apply(mu1, sigma1, mu2, sigma2)
     if not (mu1.shape == sigma1.shape == mu2.shape == sigma2.shape):
         raise _lib.RLHipArgumentError("normkldivergence: the four arguments must have one shape")
     out = torch.empty_like(mu1)
@@ -233,6 +250,10 @@ def normkldivergence(mu1, sigma1, mu2, sigma2):
 def diagnormkldivergence(mu1, sigma1, mu2, sigma2):
     """diagnormkldivergence  RLCore/src/utils/distributions.jl:117-129.  arrays are storages of Julia (d, n) matrices: torch shape
     (n, d) -> (n,)."""
+    if _wants_grad(mu1, sigma1, mu2, sigma2):
+        from . import grad
+
+        return grad.DiagNormKL.apply(mu1, sigma1, mu2, sigma2)
     if not (mu1.dim() == 2 and mu1.shape == sigma1.shape == mu2.shape == sigma2.shape):
         raise _lib.RLHipArgumentError("diagnormkldivergence: the four arguments must be (n, d) tensors of one shape")
     n, d = mu1.shape
@@ -244,12 +265,91 @@ def diagnormkldivergence(mu1, sigma1, mu2, sigma2):
 def mvnormkldivergence(mu1, L1, mu2, L2):
     """mvnormkldivergence(mu1, L1, mu2, L2), the batch form  RLCore/src/utils/distributions.jl:88-109.  mu (n, da), L (n, da, da) as in
     `mvnormlogpdf` -> (n,)."""
+    if _wants_grad(mu1, L1, mu2, L2):
+        from . import grad
+
+        return grad.MvNormKL.apply(mu1, L1, mu2, L2)
     n, da = mu1.shape
     if mu2.shape != mu1.shape or tuple(L1.shape) != (n, da, da) or tuple(L2.shape) != (n, da, da):
         raise _lib.RLHipArgumentError("mvnormkldivergence: mu (n, da) and L (n, da, da) do not agree")
     out = torch.empty(n, dtype=torch.float32, device=mu1.device)
     call("rlhip_mvnormkldivergence_f32", ptr(mu1), ptr(L1), ptr(mu2), ptr(L2), da, n, ptr(out), stream_ptr())
     return out
+
+
+def _like(t, want):
+    return torch.empty_like(t) if want else None
+
+
+def vec_to_tril_backward(chol_vec, dL, da):
+    """pullback of `vec_to_tril`: chol_vec (n, nv), dL (n, da, da) [only its lower triangle is read] -> dvec (n, nv)"""
+    n, nv = chol_vec.shape
+    if nv != da * (da + 1) // 2 or tuple(dL.shape) != (n, da, da):
+        raise _lib.RLHipArgumentError(f"vec_to_tril_backward: chol_vec {tuple(chol_vec.shape)}, dL {tuple(dL.shape)}, da = {da}")
+    out = torch.empty_like(chol_vec)
+    call("rlhip_vec_to_tril_bwd_f32", ptr(chol_vec), ptr(dL), da, n, ptr(out), stream_ptr())
+    return out
+
+
+def mvnormlogpdf_backward(mu, L, x, dlogp, need=(True, True, True)):
+    """pullback of `mvnormlogpdf`: the forward arguments and dlogp shaped like the forward output -> (dmu (n, da), dL (n, da, da) with
+    zeros above the diagonal, dx like x); `need` skips outputs (None in their place).  The sums over K run in ascending order."""
+    n, da = mu.shape
+    flat = x.dim() == 2
+    K = 1 if flat else x.shape[1]
+    if (tuple(L.shape) != (n, da, da) or tuple(x.shape) != ((n, da) if flat else (n, K, da))
+            or tuple(dlogp.shape) != ((n,) if flat else (n, K))):
+        raise _lib.RLHipArgumentError(f"mvnormlogpdf_backward: mu {tuple(mu.shape)}, L {tuple(L.shape)}, x {tuple(x.shape)}, "
+                                      f"dlogp {tuple(dlogp.shape)} do not agree")
+    dmu, dL, dx = _like(mu, need[0]), _like(L, need[1]), _like(x, need[2])
+    call("rlhip_mvnormlogpdf_bwd_f32", ptr(mu), ptr(L), ptr(x), ptr(dlogp), da, K, n, ptr(dmu), ptr(dL), ptr(dx), stream_ptr())
+    return dmu, dL, dx
+
+
+def cov_gaussian_head_logp_backward(mu, chol_vec, action, dlogp, need=(True, True)):
+    """pullback of (model::CovGaussianNetwork)(state, action) onto the heads' outputs, one launch: mu (n, da), chol_vec (n, nv),
+    action (n, K, da), dlogp (n, K) -> (dmu (n, da), dvec (n, nv))"""
+    n, da = mu.shape
+    K = action.shape[1] if action.dim() == 3 else 0
+    if tuple(chol_vec.shape) != (n, da * (da + 1) // 2) or tuple(action.shape) != (n, K, da) or tuple(dlogp.shape) != (n, K):
+        raise _lib.RLHipArgumentError(f"cov_gaussian_head_logp_backward: mu {tuple(mu.shape)}, chol_vec {tuple(chol_vec.shape)}, "
+                                      f"action {tuple(action.shape)}, dlogp {tuple(dlogp.shape)} do not agree")
+    dmu, dvec = _like(mu, need[0]), _like(chol_vec, need[1])
+    call("rlhip_cov_gaussian_head_logp_bwd_f32", ptr(mu), ptr(chol_vec), ptr(action), ptr(dlogp), da, n, K, ptr(dmu), ptr(dvec),
+         stream_ptr())
+    return dmu, dvec
+
+
+def mvnormkldivergence_backward(mu1, L1, mu2, L2, dout, need=(True, True, True, True)):
+    """pullback of `mvnormkldivergence`: dout (n,) -> (dmu1, dL1, dmu2, dL2) shaped like the arguments"""
+    n, da = mu1.shape
+    if mu2.shape != mu1.shape or tuple(L1.shape) != (n, da, da) or tuple(L2.shape) != (n, da, da) or tuple(dout.shape) != (n,):
+        raise _lib.RLHipArgumentError("mvnormkldivergence_backward: mu (n, da), L (n, da, da) and dout (n,) do not agree")
+    outs = tuple(_like(t, w) for t, w in zip((mu1, L1, mu2, L2), need))
+    call("rlhip_mvnormkldivergence_bwd_f32", ptr(mu1), ptr(L1), ptr(mu2), ptr(L2), ptr(dout), da, n, *(ptr(o) for o in outs),
+         stream_ptr())
+    return outs
+
+
+def diagnormkldivergence_backward(mu1, sigma1, mu2, sigma2, dout, need=(True, True, True, True)):
+    """pullback of `diagnormkldivergence`: (n, d) arguments, dout (n,) -> (dmu1, dsigma1, dmu2, dsigma2)"""
+    if not (mu1.dim() == 2 and mu1.shape == sigma1.shape == mu2.shape == sigma2.shape) or tuple(dout.shape) != (mu1.shape[0],):
+        raise _lib.RLHipArgumentError("diagnormkldivergence_backward: four (n, d) tensors of one shape and dout (n,)")
+    n, d = mu1.shape
+    outs = tuple(_like(t, w) for t, w in zip((mu1, sigma1, mu2, sigma2), need))
+    call("rlhip_diagnormkldivergence_bwd_f32", ptr(mu1), ptr(sigma1), ptr(mu2), ptr(sigma2), ptr(dout), d, n,
+         *(ptr(o) for o in outs), stream_ptr())
+    return outs
+
+
+def normkldivergence_backward(mu1, sigma1, mu2, sigma2, dout, need=(True, True, True, True)):
+    """pullback of `normkldivergence`, elementwise: five tensors of one shape -> (dmu1, dsigma1, dmu2, dsigma2)"""
+    if not (mu1.shape == sigma1.shape == mu2.shape == sigma2.shape == dout.shape):
+        raise _lib.RLHipArgumentError("normkldivergence_backward: the five arguments must have one shape")
+    outs = tuple(_like(t, w) for t, w in zip((mu1, sigma1, mu2, sigma2), need))
+    call("rlhip_normkldivergence_bwd_f32", ptr(mu1), ptr(sigma1), ptr(mu2), ptr(sigma2), ptr(dout), mu1.numel(),
+         *(ptr(o) for o in outs), stream_ptr())
+    return outs
 
 
 def huber_loss(q, target, delta=1.0, with_grad=True):
