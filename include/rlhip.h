@@ -391,6 +391,51 @@ int32_t rlhip_diagnormkldivergence_bwd_f32(const float* mu1, const float* s1, co
 int32_t rlhip_normkldivergence_bwd_f32(const float* mu1, const float* s1, const float* mu2, const float* s2, const float* dout,
                                        int64_t n, float* dmu1_out, float* ds1_out, float* dmu2_out, float* ds2_out,
                                        rlhip_stream_t stream);
+/* The pullbacks of normlogpdf / diagnormlogpdf and of the diagonal Gaussian heads (csrc/heads_grad.hip): the reference introduces both
+ * densities as "GPU automatic differentiable" (distributions.jl:14, :26), differentiates GaussianNetwork through its log-probabilities
+ * and SoftGaussianNetwork through its actions and its log-probabilities (the reparameterisation trick, networks.jl:127-128).  Layouts as
+ * in the forward entries: mu, raw_sigma (d x n) column-major, actions (d x K x n) with element (k, j, i) at (i K + j) d + k, dlogp (K x n).
+ * d in 1 ... 64, K >= 1, n = 0 is a no-op; anything else returns RLHIP_EINVAL before any device work.  Inputs must not be NULL; every
+ * gradient output is nullable and its work is skipped.  All f32, no contraction, no atomics; every sum over the K samples of a state runs
+ * in ascending j, sequentially, in one lane, so a result does not depend on the launch geometry.  g is the upstream cotangent.
+ *   sg = clamp(raw, lo, hi);  pass = !(raw > hi) && !(raw < lo) (inclusive bounds, a NaN passes: the reference's clamp rule);
+ *   s = sg + 1.0e-8f;  draw_sigma = pass ? dsg : +0.0f -- a select, never a product: a non-finite dsg at a clamped component gives 0,
+ *   as Julia's `delta * false` does.
+ *
+ * Pullback of normlogpdf(mu, sigma, x)  distributions.jl:18-21, elementwise over n; dout f32[n].  s = sigma + 1.0e-8f:
+ *   z = (x - mu) / s;  w = z / s;  dmu = g w;  dx = -(g w);  dsigma = g ((z z - 1.0f) / s) */
+int32_t rlhip_normlogpdf_bwd_f32(const float* mu, const float* sigma, const float* x, const float* dout, int64_t n, float* dmu_out,
+                                 float* dsigma_out, float* dx_out, rlhip_stream_t stream);
+/* Pullback of diagnormlogpdf(mu, sigma, x)  distributions.jl:31-34; arrays (d x n), dout f32[n], g the column's.  s = sigma + 1.0e-8f:
+ *   v = s s;  e = x - mu;  w = e / v;  dmu = g w;  dx = -(g w);  dsigma = g (((e e) / v - 1.0f) / s)
+ * The derivative of log(prod(v)) is taken in its closed form 2 / s.  Where prod(v) overflows or underflows the forward value is already
+ * +-Inf; the closed form stays finite there, while the reference's automatic derivative (through 1 / prod(v)) would not. */
+int32_t rlhip_diagnormlogpdf_bwd_f32(const float* mu, const float* sigma, const float* x, const float* dout, int64_t d, int64_t n,
+                                     float* dmu_out, float* dsigma_out, float* dx_out, rlhip_stream_t stream);
+/* Pullback of (model)(state, action)  networks.jl:110-116, :195-201 onto the outputs of the mu / sigma sub-networks.
+ *   z = (soft || squash) ? atanhf(a) : a.  The given actions are data: they get no gradient and the tanh correction is constant.
+ *   soft = 0 (the diagnormlogpdf form):  e = z - mu;  v = s s;
+ *       dmu[k] = 0 + sum_j g_j (e / v);  dsg[k] = 0 + sum_j g_j (((e e) / v - 1.0f) / s)
+ *   soft = 1 (the normlogpdf form):  zz = (z - mu) / s;  w = zz / s;
+ *       dmu[k] = 0 + sum_j g_j w;  dsg[k] = 0 + sum_j g_j ((zz zz - 1.0f) / s) */
+int32_t rlhip_gaussian_head_logp_bwd_f32(const float* mu, const float* raw_sigma, const float* action, const float* dlogp, int64_t d,
+                                         int64_t n, int64_t K, float min_sigma, float max_sigma, int32_t squash, int32_t soft,
+                                         float* dmu_out, float* draw_sigma_out, rlhip_stream_t stream);
+/* Pullback of the sampling calls  networks.jl:64-100, :153-185.  The launch REGENERATES the draws: eps = draw k + d j of
+ * (seed, env_id_base + i, step) and z = mu + sg eps, bit for bit the forward's, so a caller keeps only mu and raw_sigma between forward
+ * and backward -- and for a tanh-squashed head this is the only exact route: tanhf saturates to +-1 at |z| of about 9, where atanhf of
+ * the saved action is +-Inf.
+ *   soft = 0 (GaussianNetwork): z is a constant (ignore_derivatives :69, :94); the soft = 0 sums above at the regenerated z.  dact must
+ *       be NULL (the actions carry no gradient; a non-NULL dact is RLHIP_EINVAL), dlogp is required.
+ *   soft = 1 (SoftGaussianNetwork, reparameterised): dact (d x K x n) and dlogp are nullable, at least one is required.
+ *       t = tanhf(z);  zz = (z - mu) / s;  w = zz / s;
+ *       dz = 0;  if dlogp: dz = g (2.0f t - w);  if dact: dz = dz + da (1.0f - t t)
+ *       dmu[k] = 0 + sum_j ((dlogp ? g w : 0) + dz);  dsg[k] = 0 + sum_j ((dlogp ? g ((zz zz - 1.0f) / s) : 0) + dz eps)
+ *       (2 t is the exact derivative of the reference's correction -2 (log 2 - z - softplus(-2 z))) */
+int32_t rlhip_gaussian_head_sample_bwd_f32(const float* mu, const float* raw_sigma, int64_t d, int64_t n, int64_t K, float min_sigma,
+                                           float max_sigma, int32_t squash, int32_t soft, uint64_t seed, uint32_t env_id_base,
+                                           uint32_t step, const float* dact, const float* dlogp, float* dmu_out,
+                                           float* draw_sigma_out, rlhip_stream_t stream);
 /* Flux.Losses.huber_loss(q, target; delta) mean-aggregated -> loss_out f32[1]; dq (nullable) = dL/dq */
 int32_t rlhip_huber_f32(const float* q, const float* target, int64_t n, float delta, float* loss_out,
                         float* dq, rlhip_stream_t stream);

@@ -7,15 +7,9 @@
 // step t = draw k + d*j of (seed, env_id_base + i, t)).  One lane per (sample j, state i): it walks the d action
 // components in index order (the reductions over dims = 1), so a launch streams 2 d + (d + 1) K floats per state --
 // HBM-bound elementwise work; consecutive lanes touch consecutive d-vectors.
-#include "ppo_sample_device.h"
+#include "head_device.h"
 
 namespace rlhip {
-
-constexpr int HEAD_MAX_D = 64;
-
-__device__ __forceinline__ float clampj(float x, float lo, float hi) { return x > hi ? hi : (x < lo ? lo : x); }
-// NNlib.softplus (un-vendored): log1p(exp(-abs(x))) + relu(x)
-__device__ __forceinline__ float softplus_nnlib(float x) { return log1pf(expf(-fabsf(x))) + (x > 0.0f ? x : 0.0f); }
 
 // running log-probability of one pre-squash sample, fed one component at a time
 template <int SOFT>

@@ -27,7 +27,7 @@ import ReinforcementLearningCore: _run, check!, forward, target, model, PreExper
 import ReinforcementLearningCore: sample
 using Random, DomainSets
 import ChainRulesCore
-using ChainRulesCore: NoTangent, unthunk
+using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
@@ -1503,6 +1503,117 @@ function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.normkldivergenc
         NoTangent(), dμ1, dσ1, dμ2, dσ2
     end
     out, normkldivergence_pullback
+end
+
+# ---- normlogpdf / diagnormlogpdf on `DevArray`s and the diagonal Gaussian heads as functions of the μ / σ sub-networks' outputs, with
+# their pullbacks (csrc/heads_grad.hip).  The reference introduces both densities as "GPU automatic differentiable" (distributions.jl:14,
+# :26), differentiates GaussianNetwork through its log-probabilities (the draw sits under `ignore_derivatives`, networks.jl:69, :94) and
+# SoftGaussianNetwork through its actions as well (the reparameterisation trick, :153-185).  Checked statically only, like the rules above.
+normlogpdf!(out::DevBuf{Float32}, mu::DevBuf{Float32}, sigma::DevBuf{Float32}, x::DevBuf{Float32}, n) =
+    chk(ccall((:rlhip_normlogpdf_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+              mu.ptr, sigma.ptr, x.ptr, out.ptr, n, stream()))
+diagnormlogpdf!(out::DevBuf{Float32}, mu::DevBuf{Float32}, sigma::DevBuf{Float32}, x::DevBuf{Float32}, d, n) =
+    chk(ccall((:rlhip_diagnormlogpdf_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, sigma.ptr, x.ptr, d, n, out.ptr, stream()))
+"pullback of normlogpdf(μ, σ, x), elementwise; each output may be `nothing`"
+normlogpdf_bwd!(dmu, dsigma, dx, mu::DevBuf{Float32}, sigma::DevBuf{Float32}, x::DevBuf{Float32}, dout::DevBuf{Float32}, n) =
+    chk(ccall((:rlhip_normlogpdf_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, sigma.ptr, x.ptr, dout.ptr, n, _ptr(dmu), _ptr(dsigma), _ptr(dx), stream()))
+"pullback of diagnormlogpdf(μ, σ, x): arrays (d, n), dout (1, n); each output may be `nothing`"
+diagnormlogpdf_bwd!(dmu, dsigma, dx, mu::DevBuf{Float32}, sigma::DevBuf{Float32}, x::DevBuf{Float32}, dout::DevBuf{Float32}, d, n) =
+    chk(ccall((:rlhip_diagnormlogpdf_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, sigma.ptr, x.ptr, dout.ptr, d, n, _ptr(dmu), _ptr(dsigma), _ptr(dx), stream()))
+"pullback of (gn::GaussianNetwork / SoftGaussianNetwork)(s, action) onto the μ / σ heads' outputs; the actions are data"
+gaussian_logp_bwd!(dmu, draw_sigma, mu::DevBuf{Float32}, raw_sigma::DevBuf{Float32}, action::DevBuf{Float32}, dlogp::DevBuf{Float32},
+                   d, n, K; min_sigma = 0f0, max_sigma = Inf32, squash = false, soft = false) =
+    chk(ccall((:rlhip_gaussian_head_logp_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float32, Float32, Int32, Int32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, raw_sigma.ptr, action.ptr, dlogp.ptr, d, n, K, min_sigma, max_sigma, squash, soft, _ptr(dmu), _ptr(draw_sigma),
+              stream()))
+"pullback of the sampling calls: the launch regenerates the draws of (seed, env_id_base, step), so nothing but μ and σ is kept.
+`dact` (SoftGaussianNetwork only) and `dlogp` may be `nothing`"
+gaussian_sample_bwd!(dmu, draw_sigma, mu::DevBuf{Float32}, raw_sigma::DevBuf{Float32}, dact, dlogp, d, n, K; min_sigma = 0f0,
+                     max_sigma = Inf32, squash = false, soft = false, seed = 0, env_id_base = 0, step = 0) =
+    chk(ccall((:rlhip_gaussian_head_sample_bwd_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float32, Float32, Int32, Int32, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              mu.ptr, raw_sigma.ptr, d, n, K, min_sigma, max_sigma, squash, soft, seed, env_id_base, step, _ptr(dact), _ptr(dlogp),
+              _ptr(dmu), _ptr(draw_sigma), stream()))
+
+function ReinforcementLearningCore.normlogpdf(μ::DevArray{N}, σ::DevArray{N}, x::DevArray{N}) where {N}   # distributions.jl:18-21
+    size(μ) == size(σ) == size(x) || throw(DimensionMismatch("normlogpdf: μ $(size(μ)), σ $(size(σ)), x $(size(x))"))
+    out = _like(x)
+    normlogpdf!(out.buf, μ.buf, σ.buf, x.buf, prod(size(x)))
+    out
+end
+function ReinforcementLearningCore.diagnormlogpdf(μ::DevMatrix, σ::DevMatrix, x::DevMatrix)              # distributions.jl:31-34
+    size(μ) == size(σ) == size(x) || throw(DimensionMismatch("diagnormlogpdf: μ $(size(μ)), σ $(size(σ)), x $(size(x))"))
+    d, n = size(μ)
+    out = DevArray(1, n)
+    diagnormlogpdf!(out.buf, μ.buf, σ.buf, x.buf, d, n)
+    out
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.normlogpdf), μ::DevArray{N}, σ::DevArray{N}, x::DevArray{N}) where {N}
+    out = ReinforcementLearningCore.normlogpdf(μ, σ, x)
+    function normlogpdf_pullback(dout)
+        dμ, dσ, dx = _like(μ), _like(σ), _like(x)
+        normlogpdf_bwd!(dμ.buf, dσ.buf, dx.buf, μ.buf, σ.buf, x.buf, unthunk(dout).buf, prod(size(x)))
+        NoTangent(), dμ, dσ, dx
+    end
+    out, normlogpdf_pullback
+end
+function ChainRulesCore.rrule(::typeof(ReinforcementLearningCore.diagnormlogpdf), μ::DevMatrix, σ::DevMatrix, x::DevMatrix)
+    out = ReinforcementLearningCore.diagnormlogpdf(μ, σ, x)
+    d, n = size(μ)
+    function diagnormlogpdf_pullback(dout)
+        dμ, dσ, dx = _like(μ), _like(σ), _like(x)
+        diagnormlogpdf_bwd!(dμ.buf, dσ.buf, dx.buf, μ.buf, σ.buf, x.buf, unthunk(dout).buf, d, n)
+        NoTangent(), dμ, dσ, dx
+    end
+    out, diagnormlogpdf_pullback
+end
+
+"(gn)(s, action) on the heads' outputs: μ, raw σ (d, n), action (d, K, n) -> logp (1, K, n).  A (state, action) call is `pre`, `μ`, `σ`
+followed by this function, and this function carries the `rrule`."
+function gaussian_head_logp(μ::DevMatrix, σ::DevMatrix, action::DevArray3; kw...)
+    d, K, n = size(action)
+    logp = DevArray(1, K, n)
+    gaussian_logp!(logp.buf, μ.buf, σ.buf, action.buf, d, n, K; kw...)
+    logp
+end
+"the sampling calls on the heads' outputs -> actions (d, K, n), logp (1, K, n); keywords as `gaussian_sample!`"
+function gaussian_head_sample(μ::DevMatrix, σ::DevMatrix, K::Integer; kw...)
+    d, n = size(μ)
+    action, logp = DevArray(d, K, n), DevArray(1, K, n)
+    gaussian_sample!(action.buf, logp.buf, μ.buf, σ.buf, d, n, K; kw...)
+    action, logp
+end
+function ChainRulesCore.rrule(::typeof(gaussian_head_logp), μ::DevMatrix, σ::DevMatrix, action::DevArray3; kw...)
+    out = gaussian_head_logp(μ, σ, action; kw...)
+    d, K, n = size(action)
+    function gaussian_head_logp_pullback(dlogp)
+        dμ, dσ = _like(μ), _like(σ)
+        gaussian_logp_bwd!(dμ.buf, dσ.buf, μ.buf, σ.buf, action.buf, unthunk(dlogp).buf, d, n, K; kw...)
+        NoTangent(), dμ, dσ, NoTangent()
+    end
+    out, gaussian_head_logp_pullback
+end
+"soft = false: the actions carry no tangent (`ignore_derivatives`) and only the log-probabilities' cotangent is used; soft = true: the
+cotangents of both outputs enter, and one that is a `ZeroTangent` / `NoTangent` is handed over as NULL"
+function ChainRulesCore.rrule(::typeof(gaussian_head_sample), μ::DevMatrix, σ::DevMatrix, K::Integer; soft = false, kw...)
+    out = gaussian_head_sample(μ, σ, K; soft, kw...)
+    d, n = size(μ)
+    _buf(t) = t isa AbstractZero ? nothing : unthunk(t).buf
+    function gaussian_head_sample_pullback(Δ)
+        dact, dlogp = Δ
+        dμ, dσ = _like(μ), _like(σ)
+        gaussian_sample_bwd!(dμ.buf, dσ.buf, μ.buf, σ.buf, soft ? _buf(dact) : nothing, _buf(dlogp), d, n, K; soft, kw...)
+        NoTangent(), dμ, dσ, NoTangent()
+    end
+    out, gaussian_head_sample_pullback
 end
 
 # ---- the same rows on the REFERENCE's types (round 4): what a user of the reference writes keeps working when the values /

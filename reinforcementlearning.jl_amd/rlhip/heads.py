@@ -5,7 +5,13 @@ Reference: RLCore/src/utils/networks.jl -- `GaussianNetwork(pre, μ, σ; min_σ,
 (`HipApproximator.forward`, `ops.mlp2_forward`, ...) that return (features, batch) matrices in the reference's
 column-major sense, i.e. torch tensors of shape (batch, features) whose memory is (d x n) column-major; the head itself
 -- clamp, sampling, squash, log-probability with the tanh correction -- is one launch (csrc/heads.hip).  `rng` is the
-shared Philox NORMAL stream: (seed, env_id_base + column, step) with `step` advancing by one per sampling call."""
+shared Philox NORMAL stream: (seed, env_id_base + column, step) with `step` advancing by one per sampling call.
+
+With torch modules as `mu` / `sigma` both heads are trainable: while autograd is recording and a head output requires a gradient, the
+log-probabilities of `net(state, action)` and of the sampling calls are pulled back in one launch (rlhip/grad.py, csrc/heads_grad.hip),
+with values bit-identical to the plain path.  A GaussianNetwork's sampled actions carry no gradient (`ignore_derivatives` :69, :94); a
+SoftGaussianNetwork's actions do (the reparameterisation trick :153-185): the backward launch regenerates the draws from
+(seed, env_id_base, step), so no noise tensor is kept.  Given actions are data: one that requires a gradient is refused."""
 import torch
 
 from . import ops
@@ -63,20 +69,27 @@ class GaussianNetwork:
         mu, raw = self.heads(state)
         d, n = mu.shape
         act = action.permute(2, 1, 0).contiguous() if three else action.t().contiguous().reshape(n, 1, d)
-        K = act.shape[1]
-        out = torch.empty((n, K), dtype=torch.float32, device=mu.device)
+        if _wants_grad(act):
+            raise NotImplementedError("the actions given to (model)(state, action) are data here: they get no gradient (detach them)")
         mu_s, raw_s = _cm(mu), _cm(raw)  # keep the transposed copies alive across the (asynchronous) call
-        call("rlhip_gaussian_head_logp_f32", ptr(mu_s), ptr(raw_s), ptr(act), d, n, K, self.min_sigma,
-             self.max_sigma, self.squash, self.soft, ptr(out), stream_ptr())
+        if _wants_grad(mu_s, raw_s):
+            from . import grad
+
+            out = grad.GaussianHeadLogp.apply(mu_s, raw_s, act, self.min_sigma, self.max_sigma, self.squash, self.soft)
+        else:
+            out = gaussian_logp(mu_s, raw_s, act, self.min_sigma, self.max_sigma, self.squash, self.soft)
         return out.t().unsqueeze(0) if three else out.reshape(1, n)
 
     def _sample(self, mu, raw, K, want_logp):
-        d, n = mu.shape
-        act = torch.empty((n, K, d), dtype=torch.float32, device=mu.device)
-        lp = torch.empty((n, K), dtype=torch.float32, device=mu.device) if want_logp else None
+        """-> actions (n, K, d), logp (n, K) or None: the storages of the reference's arrays"""
         mu_s, raw_s = _cm(mu), _cm(raw)  # keep the transposed copies alive across the (asynchronous) call
-        call("rlhip_gaussian_head_sample_f32", ptr(mu_s), ptr(raw_s), d, n, K, self.min_sigma, self.max_sigma,
-             self.squash, self.soft, self.seed, self.env_id_base, self.step, ptr(act), ptr(lp), stream_ptr())
+        args = (K, self.min_sigma, self.max_sigma, self.squash, self.soft, self.seed, self.env_id_base, self.step, want_logp)
+        if (want_logp or self.soft) and _wants_grad(mu_s, raw_s):  # a GaussianNetwork's actions alone carry no gradient
+            from . import grad
+
+            act, lp = grad.GaussianHeadSample.apply(mu_s, raw_s, *args)
+        else:
+            act, lp = gaussian_sample(mu_s, raw_s, *args)
         self.step += 1
         return act, lp
 
@@ -174,6 +187,26 @@ class CovGaussianNetwork:
             act, lp, L = cov_sample(mu_s, vec_s, K, self.seed, self.env_id_base, self.step, want_logp, want_L)
         self.step += 1
         return (act, lp, L) if want_L else (act, lp)
+
+
+def gaussian_logp(mu_s, raw_s, act, min_sigma, max_sigma, squash, soft):
+    """the (state, action) launch on storages: mu_s, raw_s (n, d), act (n, K, d) -> logp (n, K); no autograd"""
+    n, d = mu_s.shape
+    K = act.shape[1]
+    out = torch.empty((n, K), dtype=torch.float32, device=mu_s.device)
+    call("rlhip_gaussian_head_logp_f32", ptr(mu_s), ptr(raw_s), ptr(act), d, n, K, min_sigma, max_sigma, squash, soft, ptr(out),
+         stream_ptr())
+    return out
+
+
+def gaussian_sample(mu_s, raw_s, K, min_sigma, max_sigma, squash, soft, seed, env_id_base, step, want_logp):
+    """the sampling launch on storages -> actions (n, K, d), logp (n, K) or None; no autograd"""
+    n, d = mu_s.shape
+    act = torch.empty((n, K, d), dtype=torch.float32, device=mu_s.device)
+    lp = torch.empty((n, K), dtype=torch.float32, device=mu_s.device) if want_logp else None
+    call("rlhip_gaussian_head_sample_f32", ptr(mu_s), ptr(raw_s), d, n, K, min_sigma, max_sigma, squash, soft, seed, env_id_base, step,
+         ptr(act), ptr(lp), stream_ptr())
+    return act, lp
 
 
 def cov_logp(mu_s, vec_s, act):

@@ -183,6 +183,10 @@ def clip_adam_(params, grad, m, v, beta_pow, grad_scale=1.0, clip_norm=0.0, lr=1
 
 
 def normlogpdf(mu, sigma, x):
+    if _wants_grad(mu, sigma, x):
+        from . import grad
+
+        return grad.NormLogPdf.apply(mu, sigma, x)
     out = torch.empty_like(x)
     call("rlhip_normlogpdf_f32", ptr(mu), ptr(sigma), ptr(x), ptr(out), x.numel(), stream_ptr())
     return out
@@ -190,6 +194,10 @@ def normlogpdf(mu, sigma, x):
 
 def diagnormlogpdf(mu, sigma, x):
     """arrays are storages of Julia (d, n) matrices: torch shape (n, d)."""
+    if _wants_grad(mu, sigma, x):
+        from . import grad
+
+        return grad.DiagNormLogPdf.apply(mu, sigma, x)
     n, d = mu.shape
     out = torch.empty(n, dtype=torch.float32, device=mu.device)
     call("rlhip_diagnormlogpdf_f32", ptr(mu), ptr(sigma), ptr(x), d, n, ptr(out), stream_ptr())
@@ -350,6 +358,56 @@ def normkldivergence_backward(mu1, sigma1, mu2, sigma2, dout, need=(True, True, 
     call("rlhip_normkldivergence_bwd_f32", ptr(mu1), ptr(sigma1), ptr(mu2), ptr(sigma2), ptr(dout), mu1.numel(),
          *(ptr(o) for o in outs), stream_ptr())
     return outs
+
+
+def normlogpdf_backward(mu, sigma, x, dout, need=(True, True, True)):
+    """pullback of `normlogpdf`, elementwise: four tensors of one shape -> (dmu, dsigma, dx); `need` skips outputs (None in their place)"""
+    if not (mu.shape == sigma.shape == x.shape == dout.shape):
+        raise _lib.RLHipArgumentError("normlogpdf_backward: the four arguments must have one shape")
+    outs = tuple(_like(t, w) for t, w in zip((mu, sigma, x), need))
+    call("rlhip_normlogpdf_bwd_f32", ptr(mu), ptr(sigma), ptr(x), ptr(dout), x.numel(), *(ptr(o) for o in outs), stream_ptr())
+    return outs
+
+
+def diagnormlogpdf_backward(mu, sigma, x, dout, need=(True, True, True)):
+    """pullback of `diagnormlogpdf`: three (n, d) tensors of one shape, dout (n,) -> (dmu, dsigma, dx); d <= 64, the heads' bound"""
+    if not (mu.dim() == 2 and mu.shape == sigma.shape == x.shape) or tuple(dout.shape) != (mu.shape[0],):
+        raise _lib.RLHipArgumentError("diagnormlogpdf_backward: three (n, d) tensors of one shape and dout (n,)")
+    n, d = mu.shape
+    outs = tuple(_like(t, w) for t, w in zip((mu, sigma, x), need))
+    call("rlhip_diagnormlogpdf_bwd_f32", ptr(mu), ptr(sigma), ptr(x), ptr(dout), d, n, *(ptr(o) for o in outs), stream_ptr())
+    return outs
+
+
+def gaussian_head_logp_backward(mu, raw_sigma, action, dlogp, min_sigma, max_sigma, squash, soft, need=(True, True)):
+    """pullback of (model::GaussianNetwork / SoftGaussianNetwork)(state, action) onto the heads' outputs, one launch: mu, raw_sigma (n, d),
+    action (n, K, d) [data: no gradient], dlogp (n, K) -> (dmu, draw_sigma), both (n, d).  The sums over K run in ascending order."""
+    n, d = mu.shape
+    K = action.shape[1] if action.dim() == 3 else 0
+    if raw_sigma.shape != mu.shape or tuple(action.shape) != (n, K, d) or tuple(dlogp.shape) != (n, K):
+        raise _lib.RLHipArgumentError(f"gaussian_head_logp_backward: mu {tuple(mu.shape)}, raw_sigma {tuple(raw_sigma.shape)}, "
+                                      f"action {tuple(action.shape)}, dlogp {tuple(dlogp.shape)} do not agree")
+    dmu, draw = _like(mu, need[0]), _like(raw_sigma, need[1])
+    call("rlhip_gaussian_head_logp_bwd_f32", ptr(mu), ptr(raw_sigma), ptr(action), ptr(dlogp), d, n, K, float(min_sigma),
+         float(max_sigma), int(squash), int(soft), ptr(dmu), ptr(draw), stream_ptr())
+    return dmu, draw
+
+
+def gaussian_head_sample_backward(mu, raw_sigma, K, min_sigma, max_sigma, squash, soft, seed, env_id_base, step, dact=None, dlogp=None,
+                                  need=(True, True)):
+    """pullback of the sampling calls, one launch that regenerates the draws of (seed, env_id_base, step): mu, raw_sigma (n, d), dact
+    (n, K, d) or None [SoftGaussianNetwork only: a GaussianNetwork's actions carry no gradient], dlogp (n, K) or None
+    -> (dmu, draw_sigma), both (n, d)"""
+    n, d = mu.shape
+    if (raw_sigma.shape != mu.shape or (dact is not None and tuple(dact.shape) != (n, K, d))
+            or (dlogp is not None and tuple(dlogp.shape) != (n, K))):
+        raise _lib.RLHipArgumentError(f"gaussian_head_sample_backward: mu {tuple(mu.shape)}, raw_sigma {tuple(raw_sigma.shape)}, K = {K}, "
+                                      f"dact {None if dact is None else tuple(dact.shape)}, "
+                                      f"dlogp {None if dlogp is None else tuple(dlogp.shape)} do not agree")
+    dmu, draw = _like(mu, need[0]), _like(raw_sigma, need[1])
+    call("rlhip_gaussian_head_sample_bwd_f32", ptr(mu), ptr(raw_sigma), d, n, K, float(min_sigma), float(max_sigma), int(squash),
+         int(soft), seed, env_id_base, step, ptr(dact), ptr(dlogp), ptr(dmu), ptr(draw), stream_ptr())
+    return dmu, draw
 
 
 def huber_loss(q, target, delta=1.0, with_grad=True):
