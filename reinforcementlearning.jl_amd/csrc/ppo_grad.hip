@@ -187,6 +187,11 @@ struct ApplyArgs {
 // APPLY: the last-arriving workgroup (agent-scope release/acquire around a device counter) computes the
 // global norm from the per-block partials, clips, and runs Adam on all parameters -- one launch instead
 // of reduce + clip_adam.
+// The chain of a launch (APPLY_GRID, profiles/tail_chain.md): 16 waves sum their groups' rows (a walked row pointer, full
+// batches of unconditional loads: 16 loads + 16 adds per thread at 256 rows) -> LDS + ONE barrier -> wave 0 alone: group sums,
+// grad store, Float64 sum of squares -> epoch load, two granule stores -> loads of m / v / parameter / beta powers / epoch (in
+// flight while the granules travel) -> poll -> norm, Adam, five adjacent stores (the record-image slot was computed at kernel
+// entry, in 32 bits) -> departure count.
 constexpr int RP = 64;         // parameters per reduce workgroup = the lanes of wave 0, which continues alone after the reduction
                                // (measured per optimiser step of the headline workload: RP 32 -> 34.7 us, 64 -> 31.9 us, 128 -> 32.7 us)
 constexpr int RG = 1024 / RP;  // groups of partial rows per workgroup (RP x RG = 1024 threads)
@@ -224,19 +229,55 @@ __global__ __launch_bounds__(1024) void reduce_apply_kernel(const float* __restr
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     long long ts[6] = {0, 0, 0, 0, 0, 0};
     if (APPLY == APPLY_GRID && ap.dbg) ts[0] = __builtin_amdgcn_s_memtime();
-    const int pl = threadIdx.x % RP, grp = threadIdx.x / RP;  // RG groups of RP parameters
+    // RG groups of RP parameters; a group is a wave (RP == 64), so its row range is wave-uniform -- and provably so
+    const int pl = threadIdx.x % RP, grp = __builtin_amdgcn_readfirstlane(threadIdx.x / RP);
     const int p = blockIdx.x * RP + pl;
     const int per = (nb + RG - 1) / RG;
     const int b0 = grp * per, b1 = min(nb, b0 + per);
+
+    // ---- wave 0 of the applying variants: the slot of this lane's parameter in the unit-record image depends on p alone.  It is
+    // computed HERE, in 32 bits (record_slot32.h), while the other waves issue their row loads, and pinned so that it is not sunk
+    // back behind the Adam stores: after the barrier the wave runs alone on its SIMD, and the 64-bit `%` and `/` of record_slot
+    // stood there as ~440 instructions between the parameter store and the store into the image, with nothing to hide them.
+    // (The loads of the tail -- m / v / parameter, beta powers, epoch -- stay where they are: issued here as well, so that the
+    // poll follows the publication at once, the launch got SLOWER, 6.1 -> 6.7 us: profiles/tail_chain.md section 3.)
+    unsigned int slot = 0u;
+    if ((APPLY == APPLY_GRID || APPLY == APPLY_XCHG) && grp == 0) {
+        if (p < np) slot = record_slot32((uint32_t)p, (uint32_t)ap.h, (uint32_t)ap.ns, (uint32_t)ap.nout, (uint32_t)ap.np_a);
+        asm volatile("" : "+v"(slot));
+    }
+
+    // ---- the group's rows b0 .. b1 - 1 of column p, added in ascending order.  A row pointer walks by np floats (no per-row
+    // multiply); a full batch issues its loads unconditionally, all of them before the first add (one memory latency per
+    // batch), and the batch width follows the wave-uniform row count: nb = 256 is exactly 16 loads and 16 adds per thread,
+    // nb = 512 exactly 32.  A ragged rest (nb no multiple of RG, the last group short or empty) takes the guarded batch; its
+    // missing rows add +0.0f, which changes no bit (acc starts at +0.0f and so is never -0.0f).
     float acc = 0.f;
-    if (p < np) {
-        // all loads of a 32-partial batch are issued before the first add (one memory latency per batch)
-        for (int bb = b0; bb < b1; bb += 32) {
+    const int cnt = b1 - b0;  // <= 0: an empty group
+    if (p < np && cnt > 0) {
+        const float* row = partials + (int64_t)b0 * np + p;
+        int left = cnt;
+        for (; left >= 32; left -= 32) {
             float t[32];
 #pragma unroll
-            for (int q = 0; q < 32; ++q) t[q] = (bb + q < b1) ? partials[(int64_t)(bb + q) * np + p] : 0.f;
+            for (int q = 0; q < 32; ++q, row += np) t[q] = *row;
 #pragma unroll
             for (int q = 0; q < 32; ++q) acc += t[q];
+        }
+        if (left >= 16) {
+            float t[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q, row += np) t[q] = *row;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc += t[q];
+            left -= 16;
+        }
+        if (left > 0) {
+            float t[15];
+#pragma unroll
+            for (int q = 0; q < 15; ++q, row += np) t[q] = (q < left) ? *row : 0.f;
+#pragma unroll
+            for (int q = 0; q < 15; ++q) acc += t[q];
         }
     }
     if (APPLY == APPLY_GRID && ap.dbg) ts[1] = __builtin_amdgcn_s_memtime();
@@ -361,7 +402,7 @@ __global__ __launch_bounds__(1024) void reduce_apply_kernel(const float* __restr
             ap.v[p] = vi;
             ap.params[p] = pn;
             grad[p] = g1;
-            ap.packed[record_slot(p, ap.h, ap.ns, ap.nout, ap.np_a)] = pn;
+            ap.packed[slot] = pn;
         }
         if (lane == 0) {  // (no release fence: see APPLY_GRID's departure)
             unsigned int prev = __hip_atomic_fetch_add(ap.counter + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -406,7 +447,12 @@ __global__ __launch_bounds__(1024) void reduce_apply_kernel(const float* __restr
         // 3.1 us of a 9.7 us launch by the stamps of tools/grad_timeline.py).
         if (wv != 0) return;
         const bool own = p < np;
-        // operands of this lane's parameter do not depend on the exchange: issue the loads first
+        // operands of this lane's parameter do not depend on the exchange: their loads are issued behind the publication and
+        // are in flight while the granules travel.  That round trip is not a loss: with the loads (and the one epoch load) moved
+        // to kernel entry, so that the poll follows the publication at once, the poll phase took 1.0 us longer and the launch
+        // 0.5 us (profiles/tail_chain.md section 3; supposed cause: the first poll round of every workgroup finds almost no
+        // granule yet, and the failed rounds queue on the few lines the granule stores are still travelling to) -- so the
+        // loads stay here, and the epoch is read twice.
         const float m0 = own ? ap.m[p] : 0.0f, v0 = own ? ap.v[p] : 0.0f, p0 = own ? ap.params[p] : 0.0f;
         const float c1 = 1.0f - ap.beta_pow[0], c2 = 1.0f - ap.beta_pow[1];
         typedef unsigned long long u64;
@@ -439,7 +485,7 @@ __global__ __launch_bounds__(1024) void reduce_apply_kernel(const float* __restr
             ap.v[p] = vi;
             ap.params[p] = pn;
             grad[p] = g1;
-            ap.packed[record_slot(p, ap.h, ap.ns, ap.nout, ap.np_a)] = pn;
+            ap.packed[slot] = pn;
         }
         if (ap.dbg && lane == 0) {
             ts[5] = __builtin_amdgcn_s_memtime();

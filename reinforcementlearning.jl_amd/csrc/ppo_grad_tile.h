@@ -34,6 +34,7 @@
 #pragma once
 #include "mfma_common.h"
 #include "ppo_common.h"
+#include "record_slot32.h"
 
 namespace rlhip {
 
@@ -702,7 +703,9 @@ __device__ __forceinline__ void grad_fold(char* smem, const TeamLds& L, const Te
     }
 }
 
-// position of flat parameter q in the unit-record copy (see pack_records)
+// position of flat parameter q in the unit-record copy (see pack_records).  The Adam tails of ppo_grad.hip use the 32-bit
+// form, record_slot32.h (no 64-bit division on their dependent chain); tests/test_record_slot32.py holds the two equal.
+static_assert(RECORD_FLOATS == (uint32_t)REC, "record_slot32.h restates the record size");
 __device__ __forceinline__ int64_t record_slot(int64_t q, int h, int ns, int nout, int64_t np_a) {
     const int net = q >= np_a ? 1 : 0;
     const int64_t r = q - (net ? np_a : 0);

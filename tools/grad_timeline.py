@@ -3,7 +3,13 @@
 
 stamps: 0 prologue done (before publish_first_tile) | 1 tile loop entered | 2 phase 1a done | 3 phase 1b done | 4 phase 2 done |
 5 (= 4) | 6 fold done.  What is NOT between stamps -- launch, prologue loads, the partial-row stores and the drain -- is the
-launch's event time minus the stamped span."""
+launch's event time minus the stamped span.
+
+reduce_apply_kernel<APPLY_GRID> (lane 0 of wave 0): 0 kernel entry (the record-image slot of the lane's parameter is computed
+behind it, inside the first phase) | 1 row loads + adds done | 2 barrier passed | 3 group sums, grad store, sum of squares, epoch
+load, granule stores, and the loads of m / v / parameter / beta powers / epoch ISSUED (not waited for) | 4 poll passed | 5 norm,
+Adam and the five stores done.  ts[3] brackets what it did before profiles/tail_chain.md: moving those loads to kernel entry was
+measured and not shipped."""
 import os
 import sys
 
