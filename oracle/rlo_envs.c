@@ -11,12 +11,19 @@
 #define CAT2(a, b) a##b
 #define CAT(a, b) CAT2(a, b)
 
+/* sin / cos of a Float32: Julia's sin(::Float32) / cos(::Float32) are double-precision kernels behind a Float32 interface
+ * (Base special/trig.jl: the argument is widened, reduced and evaluated in Float64, the result rounded ONCE).  Restated as
+ * the Float64 libm value rounded once.  The host's sinf / cosf (glibc: <= 0.56 ulp) give another last bit for ~0.2 % of the
+ * arguments -- tests/test_env_reference.py compares this file with an independent model and shows every such value. */
+static inline float sin_f32arg(float x) { return (float)sin((double)x); }
+static inline float cos_f32arg(float x) { return (float)cos((double)x); }
+
 /* ---- Float32 instantiation ---- */
 #define T float
 #define IS_F64 0
 #define NAME(x) CAT(x, _f32)
-#define SIN sinf
-#define COS cosf
+#define SIN sin_f32arg
+#define COS cos_f32arg
 #define FABS fabsf
 #include "rlo_envs_impl.h"
 #undef T

@@ -16,6 +16,13 @@ sample (t, env) is checked on its own:
                    recorded action: reward[t], terminal[t], obs[t + 1] (post-reset where terminal), and after the last step
                    the env's raw state, counters, reward and done; adv / ret bit for bit against the oracle's GAE.
 
+Injected cases (INJECT_CASES): a case may carry an `inject` field, raw state and t written into the env before the first
+launch (HipVecEnv.set_raw_state / oracle.VecEnv.set_state); the audit takes the pre-launch raw state at t = 0 anyway.  They
+start one MountainCar and one CartPole env set per rollout kernel (the three-layer kernels take CartPole only) on the
+goal / x-threshold rows of tests/env_edge_cases.py with max_steps far away: the only terminations the rollout kernels met
+outside CartPole were truncations.  check_injected() adds what these cases are for.  They are a list of their own: the
+shape rules of CASES (T > 32 or T = 16 for the split kernel, max_steps 5 .. 20) do not apply to them.
+
 Pendulum reconstruction (the route taken: atan2): the observation holds (sin, cos, thetadot) of an unwrapped angle.
 theta = atan2(sin, cos) in Float64, moved by the multiple of 2 pi that brings it next to the angle the oracle's previous step
 (or, at t = 0, the raw state before the launch) arrived at, rounded to Float32; where several neighbouring Float32
@@ -36,6 +43,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 import bf16_learner_matrix as MB
+import env_edge_cases as EDGE
 import f32_learner_matrix as MF
 import oracle
 
@@ -108,6 +116,62 @@ def _finish(cases):
 
 CASES = _finish(_f32_cases() + _bf16_cases())
 MATRIX_IDS = {r["id"] for r in MF.ROLLOUT} | {r["id"] for r in MB.PPO3 + MB.PPO3W if "rollout" in r["id"]}
+
+
+def _inject_cases():
+    """(kernel, env) -> the first audited case of that kernel and env, restarted with T = 8 on the no-truncation grid"""
+    out = []
+    for kernel, envs in (("rollout_split_kernel", ("mountaincar", "cartpole")), ("rollout_scalar_kernel", ("mountaincar", "cartpole")),
+                         ("ppo3_rollout_kernel", ("cartpole",)), ("ppo3_rollout32_kernel", ("cartpole",)),
+                         ("ppo3w_rollout_kernel", ("cartpole",))):
+        for env in envs:
+            base = min((c for c in CASES if c["kernel"] == kernel and c["env"] == env), key=lambda c: c["n"])
+            n = base["n"]  # the smallest n the kernel's rows of this env use, with that row's hidden size and head
+            g = EDGE.grid(f"{env}-f32-{'cont' if base['continuous'] else 'disc'}-default", 1024, truncation=False)
+            # columns from the filler half of the grid (their class holds under any action), lane pattern from lane 0 on
+            cols = (512 + np.arange(n)) % 1024
+            c = dict(base, id=base["id"] + "-injected", n=n, T=8, max_steps=EDGE.NO_TRUNC_MAX_STEPS, seed=11 + len(out),
+                     env_id_base=3000 + 19 * len(out), inject=dict(s=np.ascontiguousarray(g.s[:, cols]), t=g.t[cols].copy()),
+                     edge_params=g.p)
+            out.append(c)
+    return out
+
+
+INJECT_CASES = _inject_cases()
+
+
+def apply_inject(c, env):
+    """write the case's injected rows into an oracle.VecEnv (the GPU side: HipVecEnv.set_raw_state)"""
+    if c.get("inject"):
+        env.set_state(c["inject"]["s"], c["inject"]["t"])
+
+
+def check_injected(traj, env0, c):
+    """What the injected cases are for, on the first step of a launch that started from the injected rows: at least 20 % of
+    the envs record terminal[0] = 1 and the oracle names goal / x-threshold (never the step counter) as the cause of each,
+    reward[0] = 0 there and obs[1] is the reset draw, bit for bit.  (adv / ret over those terminals: audit(), exact.)"""
+    env, p = _new_env(c), c["edge_params"]
+    env.set_state(env0["raw_state"], env0["t"])
+    env.episode[:] = env0["episode"].view(np.uint32)
+    env.step(traj["action_f"][0] if c["continuous"] else traj["action_i"][0])
+    lo, done = env.last_obs, env.done.astype(bool)
+    if c["env"] == "mountaincar":
+        cause = (lo[0] >= p["goal_pos"]) & (lo[1] >= p["goal_velocity"])
+    else:
+        cause = (np.abs(lo[0]) > p["xthreshold"]) & (np.abs(lo[2]) <= p["thetathreshold"])
+    term0 = np.asarray(traj["terminal"][0]).astype(bool)
+    fails = []
+    if not np.array_equal(term0, done):
+        fails.append(f"terminal[0] differs from the oracle at {int((term0 != done).sum())} envs")
+    if not np.array_equal(done, cause) or (env.t[~done] > 2000).any():
+        fails.append("a termination of the first step is not a goal / x-threshold one")
+    if term0.mean() < 0.2:
+        fails.append(f"only {term0.mean():.3f} of the envs terminate at the first step")
+    if (traj["reward"][0][term0] != 0).any():
+        fails.append("reward[0] != 0 at a terminal step")
+    if not np.array_equal(np.asarray(traj["obs"][1])[:, term0], env.obs()[:, term0]):
+        fails.append("obs[1] of a terminated env is not the oracle's reset draw")
+    return fails
 
 
 def na_of(c):
@@ -426,6 +490,7 @@ def oracle_rollout(c, params, periods=2, fault=None):
     n, T, ns, nout, cont = c["n"], c["T"], NS[c["env"]], nout_of(c), c["continuous"]
     p, np_a = params
     env = _new_env(c)
+    apply_inject(c, env)
     out = []
     for period in range(periods):
         vs0 = period * T

@@ -83,3 +83,35 @@ def test_rollout_audit_vs_oracle(rl, case):
         assert (resets > 0).mean() > 0.5, "hardly an episode ends inside the launches"
     else:
         assert resets.min() >= 4, "an env reset fewer than twice per launch"
+
+
+@pytest.mark.parametrize("case", A.INJECT_CASES, ids=[c["id"] for c in A.INJECT_CASES])
+def test_rollout_audit_from_injected_states(rl, case):
+    """One MountainCar and one CartPole case per rollout kernel (the three-layer kernels take CartPole only), T = 8, started
+    from the goal / x-threshold rows of tests/env_edge_cases.py with max_steps far away: the same audit and bars, and on the
+    first step at least 20 % of the envs record a terminal that the oracle attributes to the goal / the x-threshold, with
+    reward 0 and the reset draw as the next observation (rollout_audit.check_injected); adv / ret over those terminals are
+    among the audit's bit-for-bit quantities."""
+    c = case
+    env = rl.HipVecEnv(c["env"], c["n"], seed=c["seed"], env_id_base=c["env_id_base"], **A.env_kwargs(c))
+    pol = rl.PPOPolicy(env, update_freq=c["T"], hidden=c["hidden"], act=c["act"], **({"layers": 3} if c["layers"] == 3 else {}))
+    params = A.make_params(c)
+    assert pol.np == params[0].size and pol.np_actor == params[1] and pol.seed == c["seed"]
+    pol.params.copy_(torch.as_tensor(params[0]).cuda())
+    env.set_raw_state(c["inject"]["s"], c["inject"]["t"])
+    bars = A.make_bars(c)
+    for period in range(2):
+        env0 = _snapshot(env)
+        pol.rollout_()
+        torch.cuda.synchronize()
+        tr = pol.trajectory
+        traj = {k: host(getattr(tr, k)) for k in ("obs", "value", "logp", "reward", "terminal", "adv", "ret", "action_i")}
+        traj["action_f"] = host(tr.action_f)[:, 0]
+        res = A.audit(traj, env0, _snapshot(env), params, c, period * c["T"])
+        fails, summ = A.check(res, bars)
+        print(f"\n{c['id']} period {period}: " + " ".join(f"{k}={v:.3g}" for k, v in summ.items()), res["scale"])
+        assert not fails, fails
+        if period == 0:
+            assert np.array_equal(env0["raw_state"], c["inject"]["s"]) and np.array_equal(env0["t"], c["inject"]["t"])
+            fails = A.check_injected(traj, env0, c)
+            assert not fails, fails

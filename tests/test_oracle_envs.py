@@ -109,8 +109,8 @@ def test_cartpole_reference_test_config_wide_theta(dtype):
     env.set_state(s, np.zeros(n, np.int32))
     env.step(a)
     exp = _cartpole_step_restated(s, a, dtype)
-    # positions are one exact T operation each; velocities go through sinf / cosf (<= 1 ulp from numpy's rounding
-    # of the Float64 value)
+    # positions are one exact T operation each; velocities go through sin / cos (the oracle's Float32 trig is the Float64
+    # libm value rounded once; numpy's own Float32 sin / cos may differ from it by an ulp)
     assert np.array_equal(env.s[0], exp[0]) and np.array_equal(env.s[2], exp[2])
     tol = dict(rtol=2e-6, atol=1e-6) if dtype == np.float32 else dict(rtol=1e-13, atol=1e-14)
     np.testing.assert_allclose(env.s[1], exp[1], **tol)

@@ -8,8 +8,8 @@ with the file present it turns the oracle's env rows ("pari
   Float64 cases  bit for bit (both sides IEEE double arithmetic in the source's operation order; sin / cos of glibc and of
                  Julia's openlibm-derived kernels are both correctly rounded to < 1 ulp -- a last-bit difference there would
                  show up here and is then to be judged, not hidden),
-  Float32 cases  next state within 1 ulp per component (Julia evaluates sin / cos of a Float32 in double precision and rounds
-                 once; the oracle calls sinf / cosf), reward / terminal flag / step counter exactly.
+  Float32 cases  next state within 1 ulp per component (Julia evaluates sin / cos of a Float32 with double-precision kernels
+                 and rounds once; the oracle rounds the Float64 libm value once), reward / terminal flag / step counter exactly.
 
 Also checked here WITHOUT Julia: the generator script names exactly the fields this loader reads, so the two cannot drift.
 """

@@ -105,6 +105,65 @@ def test_audit_of_the_oracles_own_rollout(cid):
         assert resets.min() >= 4, "an env reset fewer than twice per launch"
 
 
+# ------------------------------------------------------------------------------------------------- injected states
+def _cpu_inject_case(cid):
+    c = next(c for c in A.INJECT_CASES if c["id"] == cid)
+    if c["n"] > 1 << 15:
+        c = dict(c, n=4097, inject=dict(s=c["inject"]["s"][:, :4097].copy(), t=c["inject"]["t"][:4097].copy()))
+    return c
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in A.INJECT_CASES])
+def test_audit_of_the_oracles_own_rollout_from_injected_states(cid):
+    """one MountainCar and one CartPole case per rollout kernel (the three-layer kernels: CartPole), started on the goal /
+    x-threshold rows of tests/env_edge_cases.py: at least 20 % of the envs end at the first step, none through max_steps"""
+    c = _cpu_inject_case(cid)
+    params = A.make_params(c)
+    for period, rollout in enumerate(A.oracle_rollout(c, params)):
+        res, fails, summ = _audit(c, params, rollout)
+        print(f"{cid} period {period}: " + " ".join(f"{k}={v:.3g}" for k, v in summ.items()))
+        assert not fails, fails
+        assert res["n_disagree"] == 0 and not res["exception"].any()
+        for q in ("reward", "env_reward", "obs", "obs_reset", "state"):
+            assert summ[q] == 0.0
+        if period == 0:
+            tr, env0 = rollout[0], rollout[1]
+            assert np.array_equal(env0["raw_state"], c["inject"]["s"]) and np.array_equal(env0["t"], c["inject"]["t"])
+            assert not A.check_injected(tr, env0, c)
+            assert 0.2 <= tr["terminal"][0].mean() <= 0.5
+            assert tr["terminal"][0].sum() >= (4 if c["n"] == 16 else 8)
+
+
+def test_injected_cases_cover_every_rollout_kernel():
+    kernels = {c["kernel"] for c in A.CASES}
+    assert {c["kernel"] for c in A.INJECT_CASES} == kernels and len(kernels) == 5
+    for k in ("rollout_split_kernel", "rollout_scalar_kernel"):
+        assert {c["env"] for c in A.INJECT_CASES if c["kernel"] == k} == {"mountaincar", "cartpole"}
+    assert all(c["T"] == 8 and c["env_id_base"] != 0 for c in A.INJECT_CASES)
+    assert not {c["id"] for c in A.INJECT_CASES} & set(IDS)
+    import test_gpu_rollout_audit as G
+
+    marks = [m for m in G.test_rollout_audit_from_injected_states.pytestmark if m.name == "parametrize"]
+    assert len(marks) == 1 and set(marks[0].kwargs["ids"]) == {c["id"] for c in A.INJECT_CASES}
+
+
+def test_check_injected_catches_a_shifted_terminal_and_a_stale_next_observation():
+    c = _cpu_inject_case("rollout-mountaincar-scalar-relu-injected")
+    params = A.make_params(c)
+    tr, env0, _, _ = A.oracle_rollout(c, params, periods=1)[0]
+    assert not A.check_injected(tr, env0, c)
+    bad = dict(tr, terminal=np.roll(tr["terminal"], -1, axis=0))  # terminal[0] is the next step's
+    assert A.check_injected(bad, env0, c)
+    env = A._new_env(c)
+    env.auto_reset = False
+    A.apply_inject(c, env)
+    env.episode[:] = env0["episode"].view(np.uint32)
+    env.step(tr["action_i"][0])
+    stale = dict(tr, obs=tr["obs"].copy())
+    stale["obs"][1] = env.last_obs  # the pre-reset observation recorded as the next one
+    assert A.check_injected(stale, env0, c)
+
+
 # ------------------------------------------------------------------------------------------------------- corruptions
 DISC, GAUSS, DISC3 = "rollout-cartpole-h64-tanh-head2", "rollout-pendulum-h128-relu-head1", "rollout-mountaincar-h128-relu-head3"
 
