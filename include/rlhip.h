@@ -526,7 +526,8 @@ int32_t rlhip_ring_gather(const rlhip_ring* rb_host, const int64_t* idx, int64_t
                           rlhip_stream_t stream);
 
 /* n-step transitions -- NStepBatchSampler(n, gamma, batchsize) of RLTrajectories 0.4 (un-vendored: PARITY UNPINNED; the published
- * algorithm is restated in oracle/rlo_buffer.c).  Record rings only (Float32 observations with <= 4 components).
+ * algorithm is restated in oracle/rlo_buffer.c).  The fold serves record rings (Float32 observations with <= 4 components); frame rings
+ * have rlhip_ring_gather_nstep / rlhip_ring_gather_stacked_nstep below, and the index draw serves both.
  *   rlhip_ring_sample_indices_nstep   inds = rand(rng, 1:(length - n + 1), batchsize) per env: flat logical START indices
  *                                     (li * n_env + e with li <= length - n_step), same Philox draw as rlhip_ring_sample_indices.
  *   rlhip_ring_fold_nstep             for every start index the window li .. li + ns - 1 (ns = n_step, or up to and including the
@@ -597,7 +598,7 @@ int32_t rlhip_dueling_unfold_grad_f32(const float* grad_eff, float* grad_duel, i
  * of the first one (-1 if none).  One launch and a stream synchronisation: n_bad / first_bad are HOST pointers (first_bad may be
  * NULL).  A library built with -DRLHIP_BOUNDS_CHECK (RLHIP_EXTRA_FLAGS=-DRLHIP_BOUNDS_CHECK python .../build.py --force;
  * rlhip_ring_bounds_checked_build() = 1) runs this check inside every entry point that takes caller-supplied indices
- * (rlhip_ring_gather, rlhip_ring_gather_stacked, rlhip_dqn_grad_idx[_w]_f32, rlhip_dqn3_grad[_w]_f32 with idx) and returns
+ * (rlhip_ring_gather, rlhip_ring_gather_stacked, rlhip_ring_gather[_stacked]_nstep, rlhip_dqn_grad_idx[_w]_f32, rlhip_dqn3_grad[_w]_f32 with idx) and returns
  * RLHIP_EINVAL instead of reading outside the ring; the default build does not pay the synchronisation. */
 int32_t rlhip_ring_check_indices(const rlhip_ring* rb_host, const int64_t* idx, int64_t batch, int64_t* n_bad,
                                  int64_t* first_bad, rlhip_stream_t stream);
@@ -628,6 +629,33 @@ int32_t rlhip_hook_episode_stats(const float* reward, const uint8_t* done, int64
 int32_t rlhip_ring_gather_stacked(const rlhip_ring* rb_host, const int64_t* idx, int64_t batch, int32_t n_stack,
                                   void* s, int32_t* a, float* r, uint8_t* term, void* s_next,
                                   rlhip_stream_t stream);
+/* n-step transitions from FRAME rings (RLHIP_RING_FRAMES: UInt8 frames, Float32 observations with > 4 components) -- what
+ * rlhip_ring_fold_nstep is for record rings, as a gather: one launch, the same two frames read per sample as the 1-step gather.
+ * idx[b] = li * n_env + e with 0 <= li < length (the convention of rlhip_ring_gather): ANY stored transition is a legal start, so the
+ * indices of rlhip_ring_sample_indices_nstep and of a 1-step prioritized draw (rlhip_ring_sample_prioritized) both feed the call.
+ * The window is li .. li + ns - 1 of env e, ns = the smallest of n_step, k + 1 for the first k >= 0 with terminal[li + k] != 0, and
+ * length - li: it stops at, and includes, the first terminal step and never reads past the newest stored transition.  Outputs:
+ *     s = state frame li,  a = action[li],  term = (terminal[li + ns - 1] != 0),  s_next = state frame li + ns,
+ *     ret = discount_rewards_reduced over the window (RLCore/src/utils/basic.jl:237-319) in Float32 from the window's end,
+ *           gain = 0; for k = ns - 1 .. 0: gain = reward[li + k] + gamma * gain   (no contraction, this order, one lane),
+ *     n_used (int32[batch], nullable) = ns: the discount of the caller's target is gamma^ns (rlhip_gamma_pow(gamma, ns)).
+ *   rlhip_ring_gather_nstep          s / s_next laid out as rlhip_ring_gather lays them out for the same ring (component-major SoA;
+ *                                    frame-major when rlhip_ring_gather_is_frame_major(), then with its 16-byte alignment condition).
+ *   rlhip_ring_gather_stacked_nstep  s = stack(li), s_next = stack(li + ns), where stack(f) = frames f - n_stack + 1 .. f, oldest
+ *                                    first, a member all zeros when its frame index is negative or a terminal transition lies among the
+ *                                    transitions from that frame up to f - 1 (the rule of rlhip_ring_gather_stacked, whose
+ *                                    preconditions and (batch, n_stack, frame) layout hold here).  Every source frame of the union of
+ *                                    the two stacks is read once per sample.
+ * n_step = 1 reproduces rlhip_ring_gather / rlhip_ring_gather_stacked byte for byte in s, a, term (for stored flags 0 / 1) and s_next;
+ * ret == r then, but not byte for byte: a stored -0.0f comes back as +0.0f (r + gamma * 0), as it does from rlhip_ring_fold_nstep.
+ * RLHIP_EINVAL before any launch: n_step outside 1..32, a record ring (use rlhip_ring_fold_nstep), an empty ring, NULL s / a / ret /
+ * term / s_next / idx, the alignment conditions of the 1-step twins.  batch == 0 is RLHIP_OK.  A -DRLHIP_BOUNDS_CHECK build validates
+ * idx first. */
+int32_t rlhip_ring_gather_nstep(const rlhip_ring* rb_host, const int64_t* idx, int64_t batch, int32_t n_step, float gamma, void* s,
+                                int32_t* a, float* ret, uint8_t* term, void* s_next, int32_t* n_used, rlhip_stream_t stream);
+int32_t rlhip_ring_gather_stacked_nstep(const rlhip_ring* rb_host, const int64_t* idx, int64_t batch, int32_t n_stack, int32_t n_step,
+                                        float gamma, void* s, int32_t* a, float* ret, uint8_t* term, void* s_next, int32_t* n_used,
+                                        rlhip_stream_t stream);
 /* AtariEnv.act! 2-frame max-pool `screens[1] .= max.(screens[1], screens[2])`
  * (RLEnvs/src/environments/3rd_party/atari.jl:104-107) fused into the push of a UInt8 frame. */
 int32_t rlhip_ring_push_state_maxpool(rlhip_ring* rb_host, const void* screen1, const void* screen2,

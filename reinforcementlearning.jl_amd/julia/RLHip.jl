@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -1181,6 +1181,21 @@ gather_stacked!(t::HipTrajectory, idx::DevBuf{Int64}, batch, n_stack, s, a, r, t
     chk(ccall((:rlhip_ring_gather_stacked, LIB), Int32,
               (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
               t.rb, idx.ptr, batch, n_stack, s.ptr, a.ptr, r.ptr, term.ptr, s_next.ptr, stream()))
+# n-step transitions of a FRAME ring in one launch (include/rlhip.h: the window li .. li + ns - 1 cut at its first terminal step and at
+# the newest stored transition; ret = discount_rewards_reduced over it; n_used = ns, nullable)
+gather_nstep!(t::HipTrajectory, idx::DevBuf{Int64}, batch, n_step, γ::Float32, s, a, ret, term, s_next, n_used = nothing) =
+    chk(ccall((:rlhip_ring_gather_nstep, LIB), Int32,
+              (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              t.rb, idx.ptr, batch, n_step, γ, s.ptr, a.ptr, ret.ptr, term.ptr, s_next.ptr,
+              n_used === nothing ? C_NULL : n_used.ptr, stream()))
+gather_stacked_nstep!(t::HipTrajectory, idx::DevBuf{Int64}, batch, n_stack, n_step, γ::Float32, s, a, ret, term, s_next,
+                      n_used = nothing) =
+    chk(ccall((:rlhip_ring_gather_stacked_nstep, LIB), Int32,
+              (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Int32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, idx.ptr, batch, n_stack, n_step, γ, s.ptr, a.ptr, ret.ptr, term.ptr, s_next.ptr,
+              n_used === nothing ? C_NULL : n_used.ptr, stream()))
 push_maxpool!(t::HipTrajectory, screen1::DevBuf{UInt8}, screen2::DevBuf{UInt8}, a::DevBuf{Int32}, r::DevBuf{Float32},
               term::DevBuf{UInt8}) =
     chk(ccall((:rlhip_ring_push_transition_maxpool, LIB), Int32,
@@ -1688,6 +1703,40 @@ function sample(sf::HipStackFrames, t::HipTrajectory, inds::DevBuf{Int64})
     a, r, term = DevBuf{Int32}(b), DevBuf{Float32}(b), DevBuf{UInt8}(b)
     gather_stacked!(t, inds, b, sf.n_stack, s, a, r, term, sn)
     (state = s, action = a, reward = r, terminal = term, next_state = sn)
+end
+
+"""
+    HipNStepBatchSampler(n, γ; n_stack = 0)
+
+`NStepBatchSampler(n, γ, batchsize)` of RLTrajectories 0.4 over FRAME traces (`UInt8` images, `Float32` observations with more than
+four components; record rings fold their windows with `sample_nstep!`).  `sample(s, traces)` draws `traces.batchsize` window starts
+with `n` transitions ahead of them and gathers, in one launch, `(s_i, a_i, R, terminal, s_{i+ns})` with
+`R = discount_rewards_reduced(r_i … r_{i+ns-1}, γ)` -- `ns = n` unless a terminal step ends the window earlier -- plus `n_steps = ns`
+per sample (the target's discount is `γ^ns`).  `n_stack > 0` applies `StackFrames` at sample time as `HipStackFrames` does: `state` is
+the stack that ends at frame `i`, `next_state` the one that ends at frame `i + ns`.
+"""
+struct HipNStepBatchSampler
+    n::Int
+    γ::Float32
+    n_stack::Int
+end
+HipNStepBatchSampler(n::Integer, γ::Real; n_stack::Integer = 0) = HipNStepBatchSampler(Int(n), Float32(γ), Int(n_stack))
+function sample(s::HipNStepBatchSampler, t::HipTrajectory)
+    t.rb.layout == RING_FRAMES || throw(ArgumentError("record rings fold their n-step windows: sample_nstep!"))
+    b, fb = t.batchsize, Int(t.rb.obs_dim)
+    T = t.rb.elem_bytes == 1 ? UInt8 : Float32
+    chk(ccall((:rlhip_ring_sample_indices_nstep, LIB), Int32, (Ref{Ring}, Int64, Int32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, b, s.n, t.sampler_seed, t.draw_ctr, t.idx.ptr, stream()))
+    t.draw_ctr += 1
+    per = s.n_stack > 0 ? s.n_stack * fb : fb
+    st, sn = DevBuf{T}(b * per), DevBuf{T}(b * per)
+    a, ret, term, n_used = DevBuf{Int32}(b), DevBuf{Float32}(b), DevBuf{UInt8}(b), DevBuf{Int32}(b)
+    if s.n_stack > 0
+        gather_stacked_nstep!(t, t.idx, b, s.n_stack, s.n, s.γ, st, a, ret, term, sn, n_used)
+    else
+        gather_nstep!(t, t.idx, b, s.n, s.γ, st, a, ret, term, sn, n_used)
+    end
+    (state = st, action = a, reward = ret, terminal = term, next_state = sn, n_steps = n_used)
 end
 
 # plan!(explorer, values[, mask]) with `values` a device (na, n) SoA matrix = one column per env: the BatchExplorer form

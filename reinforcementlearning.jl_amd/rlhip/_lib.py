@@ -241,6 +241,8 @@ _PROTOS = {
     "rlhip_explorer_select_f32": (i32, [i32, vp, i64, i64, i64, i64, vp, i32, u64, u32, u32, vp, vp]),
     "rlhip_ucb_select_f32": (i32, [vp, i64, i64, i64, i64, f64, vp, i64, u64, u32, vp, vp]),
     "rlhip_ring_gather_stacked": (i32, [P(Ring), vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "rlhip_ring_gather_nstep": (i32, [P(Ring), vp, i64, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "rlhip_ring_gather_stacked_nstep": (i32, [P(Ring), vp, i64, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "rlhip_ring_push_state_maxpool": (i32, [P(Ring), vp, vp, vp]),
     "rlhip_ring_push_transition_maxpool": (i32, [P(Ring), vp, vp, vp, vp, vp, vp]),
     "rlhip_sumtree_nodes": (i64, [i64]),

@@ -119,6 +119,35 @@ def _gather_stacked(self, idx, n_stack):
     return s, a, r, t, sn
 
 
+def _nstep_outputs(self, b, shape):
+    dev = self.state.device
+    return (torch.empty(shape, dtype=self.dtype, device=dev), torch.empty(b, dtype=torch.int32, device=dev),
+            torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.uint8, device=dev),
+            torch.empty(shape, dtype=self.dtype, device=dev), torch.empty(b, dtype=torch.int32, device=dev))
+
+
+def _gather_nstep(self, idx, n_step, gamma):
+    """n-step transitions of a FRAME ring (rlhip_ring_gather_nstep, one launch): for every flat logical start index the window
+    li .. li + ns - 1 (cut at its first terminal step and at the newest stored transition)
+    -> (state li, action0 li, discount_rewards_reduced(rewards[window], gamma), terminal of the last step, state li + ns, ns),
+    states laid out as `gather` lays them out.  Record rings fold their windows instead (NStepBatchSampler.fold)."""
+    b = idx.numel()
+    s, a, ret, t, sn, n_used = _nstep_outputs(self, b, (b, self.obs_dim) if self.frame_major else (self.obs_dim, b))
+    call("rlhip_ring_gather_nstep", C.byref(self.rb), ptr(idx), b, n_step, gamma, ptr(s), ptr(a), ptr(ret), ptr(t), ptr(sn),
+         ptr(n_used), stream_ptr())
+    return s, a, ret, t, sn, n_used
+
+
+def _gather_stacked_nstep(self, idx, n_stack, n_step, gamma):
+    """`gather_nstep` with StackFrames applied at sample time (rlhip_ring_gather_stacked_nstep): state = the stack that ends at
+    frame li, next_state = the stack that ends at frame li + ns, both (b, n_stack, obs_dim), oldest first"""
+    b = idx.numel()
+    s, a, ret, t, sn, n_used = _nstep_outputs(self, b, (b, n_stack, self.obs_dim))
+    call("rlhip_ring_gather_stacked_nstep", C.byref(self.rb), ptr(idx), b, n_stack, n_step, gamma, ptr(s), ptr(a), ptr(ret), ptr(t),
+         ptr(sn), ptr(n_used), stream_ptr())
+    return s, a, ret, t, sn, n_used
+
+
 def _push_state_maxpool_(self, screen1, screen2):
     """push!(traces, (state = max.(screen1, screen2),)) -- AtariEnv's 2-frame max-pool fused into the push"""
     call("rlhip_ring_push_state_maxpool", C.byref(self.rb), ptr(screen1), ptr(screen2), stream_ptr())
@@ -132,6 +161,8 @@ def _push_transition_maxpool_(self, screen1, screen2, action0, reward, terminal)
 
 
 CircularArraySARTSTraces.gather_stacked = _gather_stacked
+CircularArraySARTSTraces.gather_nstep = _gather_nstep
+CircularArraySARTSTraces.gather_stacked_nstep = _gather_stacked_nstep
 CircularArraySARTSTraces.push_state_maxpool_ = _push_state_maxpool_
 CircularArraySARTSTraces.push_transition_maxpool_ = _push_transition_maxpool_
 
@@ -284,13 +315,19 @@ class NStepBatchSampler:
     indices with n transitions ahead of them, each window folded on the device into ONE transition
     (s_i, a_i, R = discount_rewards_reduced(r_i .. r_{i+ns-1}, gamma), any(terminal), s_{i+ns}) -- ns = n unless a terminal flag
     ends the window earlier.  `sample` returns the batch dictionary of BatchSampler; `fold` returns the folded record ring +
-    indices the DQN gradient entry points take unchanged (with gamma^n = `gamma_n` as their discount).  Record rings only.
+    indices the DQN gradient entry points take unchanged (with gamma^n = `gamma_n` as their discount): record rings.
+    On a FRAME ring (UInt8 images, wider Float32 observations) `sample` gathers the n-step transitions in one launch
+    (`traces.gather_nstep`; with `n_stack = k` the stack-at-sample form `traces.gather_stacked_nstep`) and the batch also carries
+    `n_steps`, the transitions each window used: the discount of sample b's target is gamma ** n_steps[b].
     Over CircularPrioritizedTraces(n_step = n) the starts are drawn in proportion to the masked priorities and the batch also carries
     `key` and `priority`, as BatchSampler's does; traces built for another n_step are a ValueError."""
 
-    def __init__(self, n, gamma, batchsize, seed=0):
+    def __init__(self, n, gamma, batchsize, seed=0, n_stack=None):
         if not 1 <= int(n) <= 32:
             raise ValueError("n must be in 1..32")
+        if n_stack is not None and not 1 <= int(n_stack) <= 8:
+            raise ValueError("n_stack must be in 1..8")
+        self.n_stack = None if n_stack is None else int(n_stack)
         self.n, self.gamma, self.batchsize, self.seed, self.draw_ctr = int(n), float(gamma), int(batchsize), seed, 0
         self.gamma_n = float(_lib.lib.rlhip_gamma_pow(self.gamma, self.n))
         self._folded = None
@@ -347,7 +384,21 @@ class NStepBatchSampler:
         call("rlhip_ring_fold_nstep", C.byref(traces.rb), ptr(idx), b, self.n, self.gamma, C.byref(folded.rb), ptr(iota), stream_ptr())
         return folded, iota
 
+    def _sample_frames(self, traces):
+        idx = self.sample_indices(traces)
+        self.draw_ctr += 1
+        if self.n_stack is None:
+            s, a, ret, t, sn, n_used = traces.gather_nstep(idx, self.n, self.gamma)
+        else:
+            s, a, ret, t, sn, n_used = traces.gather_stacked_nstep(idx, self.n_stack, self.n, self.gamma)
+        extra = dict(key=self.key, priority=self.priority) if self._prioritized(traces) else dict(key=idx)
+        return dict(state=s, action=a + 1, reward=ret, terminal=t.view(torch.bool), next_state=sn, n_steps=n_used, **extra)
+
     def sample(self, traces):
+        if not traces.records_layout:
+            return self._sample_frames(traces)
+        if self.n_stack is not None:
+            raise ValueError("n_stack selects the stack-at-sample gather of a frame ring; these traces are a record ring")
         folded, iota = self.fold(traces)
         s, a, r, t, sn = folded.gather(iota)
         extra = dict(key=self.key, priority=self.priority) if self._prioritized(traces) else {}
