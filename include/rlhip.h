@@ -218,9 +218,12 @@ int32_t rlhip_gae_returns_f32(float* advantages, float* returns, const float* re
 /* plan!(::EpsilonGreedyExplorer, values[, mask]) for n envs
  *   RLCore/policies/explorers/epsilon_greedy_explorer.jl:102-131 (+ findmax / find_all_max
  *   RLCore/utils/basic.jl:91-120); eps from rlhip_get_eps; GreedyExplorer (:200-205) = eps 0.
- * mask (nullable) u8, same strides as values.  actions: i32[n], 0-based.
- * draws: Philox(seed, idx = env_id_base + i, blk 0, t = step, EXPLORE): (w0,w1) -> u, w2 -> random index,
- * w3 -> tie-break index. */
+ * mask (nullable) u8, same strides as values, any non-zero byte = true.  actions: i32[n], 0-based.
+ * draws: Philox(seed, idx = env_id_base + i (mod 2^32), blk 0, t = step, EXPLORE): (w0,w1) -> u, w2 -> random index,
+ * w3 -> tie-break index.  Everywhere below: uniform Float64 = ((hi << 32 | lo) >> 11) 2^-53 of a word pair (hi first),
+ * uniform Float32 = (w >> 8) 2^-24, index in [0, c) = (w c) >> 32.
+ * Where the reference throws, index 0 is returned: rand(rng, Int[]) after find_all_max met a NaN maximum (no entry == NaN;
+ * is_break_tie only) and findall / maximum over an all-false mask. */
 int32_t rlhip_eps_greedy_select_f32(const float* values, int64_t na, int64_t n, int64_t k_stride,
                                     int64_t i_stride, const uint8_t* mask, double eps,
                                     int32_t is_break_tie, uint64_t seed, uint32_t env_id_base,
@@ -229,15 +232,26 @@ int32_t rlhip_eps_greedy_select_f32(const float* values, int64_t na, int64_t n, 
  * in Categorical(probs; check_args = false); pinned by RLCore/test/policies/explorers/epsilon_greedy_explorer.jl:45-73):
  *   probs[k] = eps / n_legal on legal actions, 0 on masked ones; + (1 - eps) on findmax(values[, mask]) (is_break_tie = 0),
  *   or + (1 - eps) / c on each of the c entries of find_all_max(values[, mask]) (is_break_tie = 1).
- * probs: f64, same (k_stride, i_stride) addressing as values.  Float64 like the reference (eps is a Float64). */
+ * probs: f64, same (k_stride, i_stride) addressing as values.  Float64 like the reference (eps is a Float64).
+ * is_break_tie with a NaN maximum: the tie set is empty, the column holds eps / n_legal only (as the reference's loop over no
+ * index); with an all-false mask (the reference throws): zeros, and 1 - eps at index 0 when is_break_tie = 0 (findmax of all
+ * typemin). */
 int32_t rlhip_eps_greedy_prob_f32(const float* values, int64_t na, int64_t n, int64_t k_stride, int64_t i_stride,
                                   const uint8_t* mask, double eps, int32_t is_break_tie, double* probs,
                                   rlhip_stream_t stream);
 /* get_eps  epsilon_greedy_explorer.jl:69-88 (host-side scalar; kind 0 = linear, 1 = exp) */
 double rlhip_get_eps(int32_t kind, double eps_stable, double eps_init, int64_t warmup_steps,
                      int64_t decay_steps, int64_t step);
-/* sample_categorical (Gumbel-max)  RLCore/utils/networks.jl:425-432, masking :466-468.
- * logp_out (nullable) f32[n] = logsoftmax(logits)[action]. */
+/* sample_categorical (Gumbel-max)  RLCore/utils/networks.jl:425-432 on logits .+ ifelse.(mask, 0f0, typemin) (:468).
+ * logp_out (nullable) f32[n] = logsoftmax(logits)[action].
+ * draws: Philox(seed, idx = env_id_base + i (mod 2^32), blk = k / 2, t = step, GUMBEL) for action k (0-based): even k takes the
+ * Float64 uniform of (w0, w1), odd k that of (w2, w3) -- one block per two actions, no word read twice; Gumbel noise
+ * -log(-log(u)) in Float64, added to the Float32 log-probability; the first maximal index wins.
+ * The mask is an ADDITION as in the reference: a masked NaN or +Inf logit becomes NaN (NaN + -Inf, Inf + -Inf), every other
+ * masked logit -Inf.  logsoftmax is the plain x - max - log(sum(exp(x - max))) with max skipping NaN: a NaN logit, a +Inf logit
+ * (Inf - Inf) and a column of -Inf only (all masked) make every log-probability NaN; action 0 is returned with a NaN logp_out.
+ * For +Inf the reference delegates to NNlib.logsoftmax, which is not vendored and may special-case it: that case is pinned
+ * here as stated, not to the reference. */
 int32_t rlhip_categorical_sample_f32(const float* logits, int64_t na, int64_t n, int64_t k_stride,
                                      int64_t i_stride, const uint8_t* mask, uint64_t seed,
                                      uint32_t env_id_base, uint32_t step, int32_t* actions,
@@ -256,12 +270,24 @@ int32_t rlhip_categorical_network_f32(const float* logits, int64_t na, int64_t n
  *   kind 0  WeightedExplorer{is_normalized}   weighted_explorer.jl:19-33  (mask: weight 0)
  *   kind 1  WeightedSoftmaxExplorer           weighted_softmax_explorer.jl:21-27  (mask: typemin)
  *   kind 2  GumbelSoftmaxExplorer             gumbel_softmax_explorer.jl:11-24  (Float32 Gumbel noise)
- * Draws: Philox(seed, idx = env_id_base + i, t = step, EXPLORE / GUMBEL); na <= 64. */
+ * draws, idx = env_id_base + i (mod 2^32), t = step:
+ *   kind 0, 1  blk 0, EXPLORE: the Float64 uniform of (w0, w1) -> t = u * sum(weights) (kind 0 with is_normalized, kind 1: t = u);
+ *              the walk `cw < t` over the Float32 running sum, w2 / w3 unused
+ *   kind 2     blk 0x8000 + k / 4, GUMBEL, for action k: the Float32 uniform of word k % 4 -- one block per four actions; the
+ *              blocks 0x8000.. keep clear of rlhip_categorical_sample_f32's (blk < 2^15 for na <= 2^16) under the same tag
+ * na <= 64 (RLHIP_EINVAL above, nothing written); kind outside 0..2 is RLHIP_EINVAL.  kind 1 / 2 use the plain softmax /
+ * logsoftmax formulas (see rlhip_categorical_sample_f32): a NaN or +Inf value or an all-false mask gives action 0; kind 0 walks
+ * whatever IEEE gives (all-zero weights: action 0; the walk stops at the first NaN or +Inf partial sum). */
 int32_t rlhip_explorer_select_f32(int32_t kind, const float* values, int64_t na, int64_t n, int64_t k_stride,
                                   int64_t i_stride, const uint8_t* mask, int32_t is_normalized, uint64_t seed,
                                   uint32_t env_id_base, uint32_t step, int32_t* actions, rlhip_stream_t stream);
 /* UCBExplorer  UCB_explorer.jl:24-30: argmax of values + c sqrt(log(step + 1) / counts) with a uniform pick among
- * ties; action_counts: f64 (na, n) device, counts[k * n + i], initialised to eps (1e-10), incremented here. */
+ * ties; action_counts: f64 (na, n) device, counts[k * n + i], initialised to eps (1e-10), incremented here.
+ * step >= 1 (Int64, the reference's p.step; 0 is RLHIP_EINVAL, nothing written).
+ * draws: Philox(seed, idx = env_id_base + i (mod 2^32), blk 0, t = step mod 2^32, EXPLORE): w0 -> tie-break index among the
+ * entries equal to the maximum, in ascending action order; w1..w3 unused.
+ * A NaN score makes the maximum NaN and the tie set empty (the reference throws at rand(rng, inds)): action 0 is returned and
+ * counts[0] incremented. */
 int32_t rlhip_ucb_select_f32(const float* values, int64_t na, int64_t n, int64_t k_stride, int64_t i_stride,
                              double c, double* action_counts, int64_t step, uint64_t seed, uint32_t env_id_base,
                              int32_t* actions, rlhip_stream_t stream);

@@ -129,7 +129,7 @@ int rlo_eps_greedy_prob_f64(const double* values, int64_t na, const uint8_t* mas
     return 0;
 }
 
-/* sample_categorical  RLCore/utils/networks.jl:425-432 (mask: logits .+= ifelse(mask, 0, typemin) :466-468)
+/* sample_categorical  RLCore/utils/networks.jl:425-432 (mask: logits .+= ifelse.(mask, 0f0, typemin) :468)
  *   log_probs = logsoftmax(logits, dims = 1)            (Float32, NNlib: x - max - log(sum(exp(x - max))))
  *   gumbels   = -log.(-log.(rand(rng, size...))) .+ log_probs   (rand -> Float64, so Float64)
  *   z         = argmax over dim 1 (first maximal index)
@@ -144,7 +144,8 @@ int rlo_categorical_sample_f32(const float* logits, int64_t na, int64_t n, const
         const uint8_t* mk = mask ? mask + i * na : 0;
         float mx = -INFINITY;
         for (int64_t k = 0; k < na; ++k) {
-            lp[k] = (mk && !mk[k]) ? -INFINITY : l[k];
+            /* :468 `logits .+= ifelse.(mask, 0f0, typemin)`: an addition -- a masked NaN / +Inf becomes NaN, not -Inf */
+            lp[k] = mk ? l[k] + (mk[k] ? 0.0f : -INFINITY) : l[k];
             if (lp[k] > mx) mx = lp[k];
         }
         float se = 0.0f;

@@ -133,6 +133,14 @@ __device__ __forceinline__ void gumbel_noise(int na, uint64_t seed, uint32_t id,
     }
 }
 
+// the masked logit as the reference forms it: `logits .+= ifelse.(mask, 0f0, typemin(eltype(logits)))` networks.jl:468 -- an
+// ADDITION, not a replacement: a masked NaN or +Inf logit becomes NaN (NaN + -Inf, Inf + -Inf) and poisons its column like an
+// unmasked one; every other masked logit becomes -Inf.  Without a mask the logit is read as it is (no addition is compiled).
+template <class V, class M>
+__device__ __forceinline__ float masked_logit(const V& l, const M& mk, int k) {
+    return mk.has() ? l(k) + (mk(k) ? 0.0f : -INFINITY) : l(k);
+}
+
 // logsoftmax (NNlib: x - max - log(sum(exp(x - max)))), Float32; Gumbel-max over log-probability + noise in Float64.
 // GN: functor k -> the Gumbel noise of action k
 // SHORT_LOG: the log of the log-sum-exp by log_f64_sampling -- bit-equal to the host libm's (the oracle's) after the Float32
@@ -144,19 +152,22 @@ template <bool SHORT_LOG = true, class V, class M, class GN>
 __device__ __forceinline__ int32_t categorical_select1(const V& l, const M& mk, int na, const GN& gn, float* logp_out) {
     float mx = -INFINITY;
     for (int k = 0; k < na; ++k) {
-        float x = (mk.has() && !mk(k)) ? -INFINITY : l(k);
+        float x = masked_logit(l, mk, k);
         if (x > mx) mx = x;
     }
     float se = 0.f;
     if (na == 2 && !mk.has()) {
         // two actions: the term of the maximum is exp(0) = 1 exactly, so ONE exponential gives the same sum bit for bit
-        // (0 + e + 1 and 0 + 1 + e are both RN(1 + e))
+        // (0 + e + 1 and 0 + 1 + e are both RN(1 + e)).  The term of the maximum is written 1 + (mx - mx): exactly 1 for every
+        // finite maximum, and NaN for a +Inf one -- exp(Inf - Inf) of the plain formula x - max - log(sum(exp(x - max))), which
+        // poisons the column (include/rlhip.h: action 0, NaN log-probability).  The difference does not depend on the
+        // exponential, so the dependent chain is as long as before.
         const float x0 = l(0), x1 = l(1);
         const float other = (x1 > x0) ? x0 : x1;
-        se = 1.0f + (float)::exp((double)(other - mx));
+        se = (1.0f + (mx - mx)) + (float)::exp((double)(other - mx));
     } else {
         for (int k = 0; k < na; ++k) {
-            float x = (mk.has() && !mk(k)) ? -INFINITY : l(k);
+            float x = masked_logit(l, mk, k);
             se += (float)::exp((double)(x - mx));  // Float64 eval, rounded once (libm-independent)
         }
     }
@@ -165,7 +176,7 @@ __device__ __forceinline__ int32_t categorical_select1(const V& l, const M& mk, 
     double bg = 0.0;
     float blp = 0.f;
     for (int k = 0; k < na; ++k) {
-        float x = (mk.has() && !mk(k)) ? -INFINITY : l(k);
+        float x = masked_logit(l, mk, k);
         float lp = (x - mx) - lse;
         double g = gn(k) + (double)lp;
         if (k == 0 || g > bg) {
