@@ -1058,6 +1058,52 @@ int32_t rlhip_ring_push_priority_nstep(const rlhip_ring* rb_host, float* tree, f
 int32_t rlhip_per_sample_fold_nstep_f32(const rlhip_ring* rb_host, const float* tree, int64_t batch, int32_t n_step, float gamma,
                                         uint64_t seed, uint32_t draw_ctr, int64_t* idx_out, int64_t* key_out, float* prio_out,
                                         rlhip_ring* folded_host, int64_t* iota_out, rlhip_stream_t stream);
+/* The same for FRAME rings (RLHIP_RING_FRAMES: UInt8 frames, Float32 observations with > 4 components; any n_env), where the n-step
+ * transition is gathered (rlhip_ring_gather_nstep / rlhip_ring_gather_stacked_nstep), not folded.  (Entry points added:
+ * RLHIP_ABI_VERSION stays 2.)
+ *   rlhip_ring_push_priority_nstep_frames   the rule, the refusals and their order of rlhip_ring_push_priority_nstep -- the newest
+ *                                    frame's n_env leaves := 0, then, if length >= n_step, the leaves of logical frame length - n_step
+ *                                    := priority; n_step = 1 leaves the tree of rlhip_ring_push_priority bit for bit -- for frame
+ *                                    rings; a record ring is RLHIP_EINVAL here as a frame ring is there.
+ *   rlhip_ring_sample_gather_nstep_prioritized / rlhip_ring_sample_gather_stacked_nstep_prioritized
+ *                                    the prioritized draw and the n-step gather of its batch in ONE launch.  idx_out / key_out /
+ *                                    prio_out are byte for byte those of rlhip_ring_sample_prioritized on the same tree, every other
+ *                                    output byte for byte that of rlhip_ring_gather_nstep / rlhip_ring_gather_stacked_nstep called
+ *                                    with those indices, on all three routes (component-major for any n_env, Float32 and UInt8;
+ *                                    frame-major; stack-at-sample).  key_out, prio_out and n_used may be NULL.  The call neither
+ *                                    knows nor needs the mask: on a tree masked for n_step every window is complete, on an unmasked
+ *                                    tree a window is cut at the newest stored transition, as the gathers define.
+ *                                    RLHIP_EINVAL before any launch: what rlhip_ring_sample_prioritized or the gather it stands for
+ *                                    refuses (n_step outside 1..32, a record ring, an empty ring, n_stack outside 1..8, n_env > 1 or
+ *                                    a frame size that is no multiple of 16 bytes for the stacked call, the alignment conditions),
+ *                                    NULL tree / idx_out / s / a / ret / term / s_next, a tree that is not 8-byte aligned, ring
+ *                                    counters out of range.  batch == 0 is RLHIP_OK.  Memory safety: the tree holds
+ *                                    rlhip_sumtree_nodes(capacity * n_env) floats and is 8-byte aligned (child pairs are read as one
+ *                                    8-byte load, as the shipped sampler reads them); every tree read is below that size, and a drawn
+ *                                    key is clamped below capacity * n_env, so every address formed from it stays inside the ring's
+ *                                    allocations for ANY tree contents; a leaf outside the logical range (no push ABI puts mass
+ *                                    there) gives a one-step window.  A -DRLHIP_BOUNDS_CHECK build has no
+ *                                    caller index to validate here.
+ *                                    Measured on the 84 x 84 UInt8 ring, capacity 2^17, full, n_step 3, n_stack 4, against the two
+ *                                    launches (profiles/per_frames_nstep.md), us per call at batch 32 / 512 / 4096: frame-major 8.95 /
+ *                                    8.55 / 27.99 against 15.50 / 14.52 / 29.95; stacked 15.73 / 23.36 / 80.34 against 18.35 / 26.33 /
+ *                                    80.33.  The frame-major kernel publishes the drawn index behind a first barrier, so that every
+ *                                    wave requests its state chunks while the window is fetched, and the next frame behind a second
+ *                                    (the one-barrier schedule measured 30.5 us at batch 4096).  The stacked call launches its fused
+ *                                    kernel for batch <= 1536 and the two launches it stands for beyond (fused measured 1.16 x / 1.10 x
+ *                                    their time at batch 2048 / 4096; timed at n_stack 4 only): same bytes either way.  The component-major route is fused at
+ *                                    every size and was not timed. */
+int32_t rlhip_ring_push_priority_nstep_frames(const rlhip_ring* rb_host, float* tree, float priority, int32_t n_step,
+                                              rlhip_stream_t stream);
+int32_t rlhip_ring_sample_gather_nstep_prioritized(const rlhip_ring* rb_host, const float* tree, int64_t batch, int32_t n_step,
+                                                   float gamma, uint64_t seed, uint32_t draw_ctr, int64_t* idx_out, int64_t* key_out,
+                                                   float* prio_out, void* s, int32_t* a, float* ret, uint8_t* term, void* s_next,
+                                                   int32_t* n_used, rlhip_stream_t stream);
+int32_t rlhip_ring_sample_gather_stacked_nstep_prioritized(const rlhip_ring* rb_host, const float* tree, int64_t batch, int32_t n_stack,
+                                                           int32_t n_step, float gamma, uint64_t seed, uint32_t draw_ctr,
+                                                           int64_t* idx_out, int64_t* key_out, float* prio_out, void* s, int32_t* a,
+                                                           float* ret, uint8_t* term, void* s_next, int32_t* n_used,
+                                                           rlhip_stream_t stream);
 
 /* ---------------------------------------------------------------------------------- MLP -- */
 /* Chain(Dense(n_in, h, act), Dense(h, n_out)) with flat parameters in Flux.destructure order:

@@ -5,7 +5,8 @@
 // The mask lives in the TREE: rlhip_ring_push_priority_nstep holds the leaves of the newest n_step - 1 transition frames at 0 and
 // hands a frame its default priority only once n_step transitions lie at or after it.  The descent of the shipped sampler never
 // enters a zero-sum subtree, so the UNCHANGED draw (rlhip_ring_sample_prioritized) returns only valid window starts, distributed as
-// p * valid / sum(p * valid): no new sampling arithmetic.
+// p * valid / sum(p * valid): no new sampling arithmetic.  rlhip_ring_push_priority_nstep_frames is the same rule for frame rings
+// (one body: the keys are `physical rt frame * n_env + e` in both layouts); their draw + gather launch is per_frames_nstep.hip.
 //
 // rlhip_per_sample_fold_nstep_f32 is that draw and the window fold (rlhip_ring_fold_nstep) in ONE launch, as dqn_sample_fold.hip is
 // for the uniform sampler: the lane that owns sample b makes the draw of sumtree_sample_kernel (sumtree_device.h's `sumtree_draw`:
@@ -68,11 +69,13 @@ __global__ __launch_bounds__(FOLD_TILE) void per_sample_fold_nstep_kernel(PerNst
 
 using namespace rlhip;
 
-extern "C" int32_t rlhip_ring_push_priority_nstep(const rlhip_ring* rb, float* tree, float priority, int32_t n_step,
-                                                  rlhip_stream_t stream) {
+// the lagged push of both layouts: the sum-tree's keys are `physical rt frame * n_env + e` whatever holds the transitions, so the
+// rule never looks at the storage; `layout` / `layout_message` say which rings the calling entry point serves
+static int32_t push_priority_nstep(const rlhip_ring* rb, float* tree, float priority, int32_t n_step, rlhip_stream_t stream,
+                                   int32_t layout, const char* layout_message) {
     RLHIP_REQUIRE(rb && tree, "bad arguments");
     RLHIP_REQUIRE(n_step >= 1 && n_step <= FOLD_MAX_NSTEP, "n_step must be in 1..32");
-    RLHIP_REQUIRE(rb->layout == RLHIP_RING_RECORDS, "n-step priorities are defined for record rings (Float32 observations, obs_dim <= 4)");
+    RLHIP_REQUIRE(rb->layout == layout, layout_message);
     RLHIP_REQUIRE(n_step <= rb->capacity, "n_step exceeds the ring's capacity: no window would ever be complete");
     RLHIP_REQUIRE(priority >= 0.0f, "priorities must be non-negative");
     RLHIP_REQUIRE(rb->len_rt >= 1, "no transition has been pushed yet");
@@ -88,6 +91,19 @@ extern "C" int32_t rlhip_ring_push_priority_nstep(const rlhip_ring* rb, float* t
     // one fill of rlhip_ring_push_priority -- the tree is a pure function of its leaves)
     const int64_t ready = (rb->head_rt + rb->len_rt - n_step) % rb->capacity;
     return rlhip_sumtree_fill_range(tree, n_leaves, ready * rb->n_env, rb->n_env, priority, stream);
+}
+
+extern "C" int32_t rlhip_ring_push_priority_nstep(const rlhip_ring* rb, float* tree, float priority, int32_t n_step,
+                                                  rlhip_stream_t stream) {
+    return push_priority_nstep(rb, tree, priority, n_step, stream, RLHIP_RING_RECORDS,
+                               "n-step priorities are defined for record rings (Float32 observations, obs_dim <= 4)");
+}
+
+extern "C" int32_t rlhip_ring_push_priority_nstep_frames(const rlhip_ring* rb, float* tree, float priority, int32_t n_step,
+                                                         rlhip_stream_t stream) {
+    return push_priority_nstep(rb, tree, priority, n_step, stream, RLHIP_RING_FRAMES,
+                               "this push serves frame rings; a record ring (Float32 observations, obs_dim <= 4) takes "
+                               "rlhip_ring_push_priority_nstep");
 }
 
 extern "C" int32_t rlhip_per_sample_fold_nstep_f32(const rlhip_ring* rb, const float* tree, int64_t batch, int32_t n_step, float gamma,

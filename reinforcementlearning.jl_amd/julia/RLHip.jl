@@ -1125,6 +1125,31 @@ function sample_fold_prioritized!(folded::HipTrajectory{Float32}, iota::DevBuf{I
               t.rb, tree.ptr, batch, n_step, γ, seed, ctr, idx.ptr, key.ptr, prio.ptr, folded.rb, iota.ptr, stream()))
     ccall((:rlhip_gamma_pow, LIB), Float32, (Float32, Int32), γ, n_step)
 end
+"`push_priority_nstep!` for FRAME traces (`UInt8` images, `Float32` observations with more than four components): the same rule"
+push_priority_nstep_frames!(t::HipTrajectory, tree::DevBuf{Float32}, p::Float32, n_step::Integer) =
+    chk(ccall((:rlhip_ring_push_priority_nstep_frames, LIB), Int32, (Ref{Ring}, Ptr{Cvoid}, Float32, Int32, Ptr{Cvoid}),
+              t.rb, tree.ptr, p, n_step, stream()))
+"""
+    sample_gather_nstep_prioritized!(idx, key, prio, t, tree, batch, n_step, γ, seed, ctr, s, a, ret, term, s_next, n_used = nothing)
+
+The prioritized draw on a FRAME ring's tree and the n-step gather of its batch in ONE launch (byte for byte `sample_prioritized!`
+followed by `gather_nstep!`); `sample_gather_stacked_nstep_prioritized!` is the same with `gather_stacked_nstep!`.
+"""
+sample_gather_nstep_prioritized!(idx::DevBuf{Int64}, key::DevBuf{Int64}, prio::DevBuf{Float32}, t::HipTrajectory, tree::DevBuf{Float32},
+                                 batch, n_step, γ::Float32, seed, ctr, s, a, ret, term, s_next, n_used = nothing) =
+    chk(ccall((:rlhip_ring_sample_gather_nstep_prioritized, LIB), Int32,
+              (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, tree.ptr, batch, n_step, γ, seed, ctr, idx.ptr, key.ptr, prio.ptr, s.ptr, a.ptr, ret.ptr, term.ptr, s_next.ptr,
+              n_used === nothing ? C_NULL : n_used.ptr, stream()))
+sample_gather_stacked_nstep_prioritized!(idx::DevBuf{Int64}, key::DevBuf{Int64}, prio::DevBuf{Float32}, t::HipTrajectory,
+                                         tree::DevBuf{Float32}, batch, n_stack, n_step, γ::Float32, seed, ctr, s, a, ret, term, s_next,
+                                         n_used = nothing) =
+    chk(ccall((:rlhip_ring_sample_gather_stacked_nstep_prioritized, LIB), Int32,
+              (Ref{Ring}, Ptr{Cvoid}, Int64, Int32, Int32, Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, tree.ptr, batch, n_stack, n_step, γ, seed, ctr, idx.ptr, key.ptr, prio.ptr, s.ptr, a.ptr, ret.ptr, term.ptr,
+              s_next.ptr, n_used === nothing ? C_NULL : n_used.ptr, stream()))
 "`inds, priorities = rand(rng, sumtree, batchsize)`: logical indices for the gather, physical keys for the write-back"
 sample_prioritized!(idx::DevBuf{Int64}, key::DevBuf{Int64}, prio::DevBuf{Float32}, t::HipTrajectory, tree, batch, seed, ctr) =
     chk(ccall((:rlhip_ring_sample_prioritized, LIB), Int32,
@@ -1641,7 +1666,8 @@ end
 device sum-tree: `push!` gives every new transition `default_priority`, `sample(traces, batchsize)` is the prioritized
 `BatchSampler` draw (`inds, priorities = rand(rng, sumtree, batchsize)`) and `traces[:priority, keys] = p` the write-back.
 `n_step > 1`: the traces serve an `NStepBatchSampler(n_step, …)` -- `push!` keeps the newest `n_step - 1` frames at priority 0
-(`push_priority_nstep!`), so every draw is a window start with its `n_step` transitions ahead.
+(`push_priority_nstep!`; over FRAME traces `push_priority_nstep_frames!`), so every draw is a window start with its `n_step`
+transitions ahead.  Frame traces are sampled with `sample(HipNStepBatchSampler(n_step, γ; n_stack), traces)`: draw and gather in one launch.
 """
 mutable struct HipPrioritizedTraces
     traces::HipTrajectory
@@ -1665,6 +1691,8 @@ function Base.push!(p::HipPrioritizedTraces, x::NamedTuple{(:state, :action, :re
     push!(p.traces, x)
     if p.n_step == 1
         push_priority!(p.traces, p.tree, p.default_priority)
+    elseif p.traces.rb.layout == RING_FRAMES
+        push_priority_nstep_frames!(p.traces, p.tree, p.default_priority, p.n_step)
     else
         push_priority_nstep!(p.traces, p.tree, p.default_priority, p.n_step)
     end
@@ -1737,6 +1765,31 @@ function sample(s::HipNStepBatchSampler, t::HipTrajectory)
         gather_nstep!(t, t.idx, b, s.n, s.γ, st, a, ret, term, sn, n_used)
     end
     (state = st, action = a, reward = ret, terminal = term, next_state = sn, n_steps = n_used)
+end
+"""
+the same over prioritized FRAME traces built with `n_step = s.n`: the draw from the masked tree and the gather are ONE launch
+(`sample_gather_nstep_prioritized!` / `sample_gather_stacked_nstep_prioritized!`), and the batch also carries `key` (for
+`traces[:priority, key] = p`, before the next push) and `priority`
+"""
+function sample(s::HipNStepBatchSampler, p::HipPrioritizedTraces)
+    t = p.traces
+    t.rb.layout == RING_FRAMES || throw(ArgumentError("record rings draw and fold their n-step windows: sample_fold_prioritized!"))
+    p.n_step == s.n || throw(ArgumentError("the traces mask windows of n_step = $(p.n_step), the sampler folds n = $(s.n)"))
+    length(p) >= s.n || throw(ArgumentError("the trajectory holds fewer than n transitions: the masked tree has no mass"))
+    b, fb = t.batchsize, Int(t.rb.obs_dim)
+    T = t.rb.elem_bytes == 1 ? UInt8 : Float32
+    per = s.n_stack > 0 ? s.n_stack * fb : fb
+    idx, key, prio = DevBuf{Int64}(b), DevBuf{Int64}(b), DevBuf{Float32}(b)
+    st, sn = DevBuf{T}(b * per), DevBuf{T}(b * per)
+    a, ret, term, n_used = DevBuf{Int32}(b), DevBuf{Float32}(b), DevBuf{UInt8}(b), DevBuf{Int32}(b)
+    if s.n_stack > 0
+        sample_gather_stacked_nstep_prioritized!(idx, key, prio, t, p.tree, b, s.n_stack, s.n, s.γ, p.seed, p.draw_ctr, st, a, ret, term,
+                                                 sn, n_used)
+    else
+        sample_gather_nstep_prioritized!(idx, key, prio, t, p.tree, b, s.n, s.γ, p.seed, p.draw_ctr, st, a, ret, term, sn, n_used)
+    end
+    p.draw_ctr += UInt32(1)
+    (state = st, action = a, reward = ret, terminal = term, next_state = sn, n_steps = n_used, key = key, priority = prio)
 end
 
 # plan!(explorer, values[, mask]) with `values` a device (na, n) SoA matrix = one column per env: the BatchExplorer form

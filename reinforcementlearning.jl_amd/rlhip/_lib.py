@@ -256,6 +256,10 @@ _PROTOS = {
     "rlhip_ring_sample_prioritized": (i32, [P(Ring), vp, i64, u64, u32, vp, vp, vp, vp]),
     "rlhip_ring_push_priority_nstep": (i32, [P(Ring), vp, f32, i32, vp]),
     "rlhip_per_sample_fold_nstep_f32": (i32, [P(Ring), vp, i64, i32, f32, u64, u32, vp, vp, vp, P(Ring), vp, vp]),
+    "rlhip_ring_push_priority_nstep_frames": (i32, [P(Ring), vp, f32, i32, vp]),
+    "rlhip_ring_sample_gather_nstep_prioritized": (i32, [P(Ring), vp, i64, i32, f32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rlhip_ring_sample_gather_stacked_nstep_prioritized": (i32, [P(Ring), vp, i64, i32, i32, f32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                                 vp, vp]),
     "rlhip_ring_sample_gather_prioritized": (i32, [P(Ring), vp, i64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "rlhip_ring_update_sample_gather_prioritized": (i32, [P(Ring), vp, vp, vp, i64, i64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "rlhip_mlp2_nparams": (i64, [i64, i64, i64]),

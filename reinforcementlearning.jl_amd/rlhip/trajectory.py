@@ -176,7 +176,7 @@ class CircularPrioritizedTraces(CircularArraySARTSTraces):
     `sample(::NStepBatchSampler, ::CircularPrioritizedTraces)` is kept in the tree (rlhip_ring_push_priority_nstep, csrc/per_nstep.hip):
     the newest n_step - 1 frames stay at priority 0 and a frame receives `default_priority` once n_step transitions lie at or after
     it, so every draw is a window start with its n transitions ahead.  Write priorities back (`set_priority_`) under keys drawn since
-    the last push.  n_step = 1, the default, is the plain push."""
+    the last push.  n_step = 1, the default, is the plain push.  Frame rings with n_step > 1: CircularPrioritizedFrameTraces."""
 
     def __init__(self, capacity, n_env=1, obs_dim=1, dtype=torch.float32, default_priority=100.0, device="cuda", n_step=1):
         self._check_n_step(n_step, capacity, dtype == torch.float32 and obs_dim <= 4)  # before anything is allocated
@@ -278,6 +278,48 @@ class CircularPrioritizedTraces(CircularArraySARTSTraces):
         return float(self.priorities[1])
 
 
+class CircularPrioritizedFrameTraces(CircularPrioritizedTraces):
+    """CircularPrioritizedTraces over a FRAME ring (UInt8 images, Float32 observations with more than four components) that serve an
+    NStepBatchSampler(n_step, ...), n_step in 1..32: the validity mask is kept in the tree by rlhip_ring_push_priority_nstep_frames
+    (the rule of the record rings' push, csrc/per_nstep.hip), and `sample_gather_nstep_prioritized` is the prioritized draw and the
+    n-step gather of its batch in ONE launch (csrc/per_frames_nstep.hip) -- with `n_stack` the stack-at-sample form, the sampler of a
+    Rainbow-style Atari agent.  Record-layout observations (Float32, obs_dim <= 4) are refused: CircularPrioritizedTraces serves them."""
+
+    @staticmethod
+    def _check_n_step(n_step, capacity, records_layout):
+        if isinstance(n_step, bool) or int(n_step) != n_step or not 1 <= int(n_step) <= 32:
+            raise ValueError("n_step must be an integer in 1..32")
+        if records_layout:
+            raise ValueError("CircularPrioritizedFrameTraces needs a frame layout (UInt8, or Float32 with obs_dim > 4); a record ring "
+                             "takes CircularPrioritizedTraces(..., n_step = n_step)")
+        if int(n_step) > capacity:
+            raise ValueError("n_step exceeds the capacity: no window would ever be complete")
+
+    def push_transition_(self, next_obs, action0, reward, terminal):
+        CircularArraySARTSTraces.push_transition_(self, next_obs, action0, reward, terminal)
+        # the newest frame := 0, the frame with n_step transitions at or after it := default_priority (n_step = 1: the plain push's tree)
+        call("rlhip_ring_push_priority_nstep_frames", C.byref(self.rb), ptr(self.priorities), self.default_priority, self.n_step,
+             stream_ptr())
+
+    def sample_gather_nstep_prioritized(self, batch, n, gamma, seed, draw_ctr, n_stack=None):
+        """the prioritized draw and the n-step gather of its batch in ONE launch (bit-identical to sample_prioritized + gather_nstep,
+        with `n_stack` + gather_stacked_nstep) -> (idx, key, priority), (state, action0, return, terminal, next_state, n_used).
+        `n` is the window the gather folds; on a tree masked for n_step = n every window is complete"""
+        dev = self.state.device
+        idx = torch.empty(batch, dtype=torch.int64, device=dev)
+        key = torch.empty(batch, dtype=torch.int64, device=dev)
+        prio = torch.empty(batch, dtype=torch.float32, device=dev)
+        if n_stack is None:
+            s, a, ret, t, sn, n_used = _nstep_outputs(self, batch, (batch, self.obs_dim) if self.frame_major else (self.obs_dim, batch))
+            call("rlhip_ring_sample_gather_nstep_prioritized", C.byref(self.rb), ptr(self.priorities), batch, n, gamma, seed, draw_ctr,
+                 ptr(idx), ptr(key), ptr(prio), ptr(s), ptr(a), ptr(ret), ptr(t), ptr(sn), ptr(n_used), stream_ptr())
+        else:
+            s, a, ret, t, sn, n_used = _nstep_outputs(self, batch, (batch, n_stack, self.obs_dim))
+            call("rlhip_ring_sample_gather_stacked_nstep_prioritized", C.byref(self.rb), ptr(self.priorities), batch, n_stack, n, gamma,
+                 seed, draw_ctr, ptr(idx), ptr(key), ptr(prio), ptr(s), ptr(a), ptr(ret), ptr(t), ptr(sn), ptr(n_used), stream_ptr())
+        return (idx, key, prio), (s, a, ret, t, sn, n_used)
+
+
 class BatchSampler:
     """BatchSampler(batchsize; rng): uniform indices with replacement (Philox SAMPLER stream); over
     CircularPrioritizedTraces: `inds, priorities = rand(rng, sumtree, batchsize)` and the batch also carries
@@ -320,7 +362,9 @@ class NStepBatchSampler:
     (`traces.gather_nstep`; with `n_stack = k` the stack-at-sample form `traces.gather_stacked_nstep`) and the batch also carries
     `n_steps`, the transitions each window used: the discount of sample b's target is gamma ** n_steps[b].
     Over CircularPrioritizedTraces(n_step = n) the starts are drawn in proportion to the masked priorities and the batch also carries
-    `key` and `priority`, as BatchSampler's does; traces built for another n_step are a ValueError."""
+    `key` and `priority`, as BatchSampler's does; traces built for another n_step are a ValueError.  Over
+    CircularPrioritizedFrameTraces(n_step = n) -- prioritized frame rings -- `sample` is the draw and the (stacked) n-step gather in
+    one launch, the same dictionary bit for bit as `sample_indices` followed by `gather_nstep` / `gather_stacked_nstep`."""
 
     def __init__(self, n, gamma, batchsize, seed=0, n_stack=None):
         if not 1 <= int(n) <= 32:
@@ -385,6 +429,14 @@ class NStepBatchSampler:
         return folded, iota
 
     def _sample_frames(self, traces):
+        if isinstance(traces, CircularPrioritizedFrameTraces) and self._prioritized(traces):  # draw + gather: one launch
+            if len(traces) < self.n:
+                raise _lib.RLHipArgumentError("the trajectory holds fewer than n transitions: the masked tree has no mass")
+            (idx, self.key, self.priority), (s, a, ret, t, sn, n_used) = traces.sample_gather_nstep_prioritized(
+                self.batchsize, self.n, self.gamma, self.seed, self.draw_ctr, self.n_stack)
+            self.draw_ctr += 1
+            return dict(state=s, action=a + 1, reward=ret, terminal=t.view(torch.bool), next_state=sn, n_steps=n_used, key=self.key,
+                        priority=self.priority)
         idx = self.sample_indices(traces)
         self.draw_ctr += 1
         if self.n_stack is None:
