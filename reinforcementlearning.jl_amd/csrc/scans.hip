@@ -195,7 +195,8 @@ static int32_t discount_impl(T* out, const T* r, int64_t n1, int64_t n2, T gamma
     if (rc) return rc;
     // empty inputs are a no-op (an empty device array has a NULL base pointer): checked before the NULL test
     if (g.n_slices == 0 || (g.len == 0 && !REDUCED)) return RLHIP_OK;
-    RLHIP_REQUIRE(out != nullptr && r != nullptr, "NULL array");
+    // the reduced form of an empty scan returns init (:256-262): its rewards are an empty array, whose base pointer is NULL
+    RLHIP_REQUIRE(out != nullptr && (r != nullptr || g.len == 0), "NULL array");
     hipLaunchKernelGGL((discount_kernel<T, REDUCED>), dim3((int)((g.n_slices + 255) / 256)), dim3(256), 0,
                        s, out, r, term, init, g.n_slices, g.len, g.elem_stride, g.slice_stride, gamma,
                        dims == 0 ? 0 : 1);
