@@ -1319,6 +1319,54 @@ int32_t rlhip_dqn_plan_f32(const float* params, int64_t ns, int64_t h, int64_t n
                            uint32_t env_id_base, uint32_t step, int32_t* actions, float* q_out,
                            rlhip_stream_t stream);
 
+/* ------------------------------------------------- DQN on observations of 5..16 components -- */
+/* (csrc/dqn_batch.hip; AcrobotRK4Env has six.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * rlhip_dqn_plan_obsn_f32: rlhip_dqn_plan_f32 for ns in 5..16 (na 1..4, h >= 1, act 0 / 1; n = 0 is a no-op; ns <= 4 or ns > 16 is
+ * RLHIP_EINVAL: 2..4 components take rlhip_dqn_plan_f32).  One lane per env.  q_out (nullable, SoA (na x n)) is byte for byte
+ * rlhip_mlp2_forward_f32 -- z = b1[j], fmaf over k ascending; q = b2, fmaf over j ascending -- and `actions` byte for byte
+ * rlhip_eps_greedy_select_f32 (no mask, no tie-break) on those values with the same (eps, seed, env_id_base, step). */
+int32_t rlhip_dqn_plan_obsn_f32(const float* params, int64_t ns, int64_t h, int64_t na, int32_t act, const float* obs, int64_t n,
+                                double eps, uint64_t seed, uint32_t env_id_base, uint32_t step, int32_t* actions, float* q_out,
+                                rlhip_stream_t stream);
+/* rlhip_dqn_grad_batch_f32: loss and flat gradient of the two-layer Float32 Q-network on a GATHERED batch -- s / s_next SoA
+ * (ns x batch) as rlhip_ring_gather, rlhip_ring_gather_nstep and rlhip_ring_sample_gather_nstep_prioritized write them from a
+ * frame-layout ring, a / r / term (batch).  ns 5..16, h a multiple of 4 and <= 256, na 1..4, act 0 / 1, batch >= 1; anything else
+ * (and a NULL array other than the three nullable ones) is RLHIP_EINVAL before any launch.  workspace: at least
+ * rlhip_dqn_batch_workspace_bytes(ns, h, na, batch) bytes (-1 for a shape this entry refuses); it needs no initialisation.
+ *
+ * Per sample i, in Float32 without contraction (oracle/rlo_learn.c rlo_dqn_loss_grad_f32):
+ *     cont = term[i] ? 0 : 1
+ *     disc = n_used ? rlhip_gamma_pow(gamma, clamp(n_used[i], 0, 32)) : gamma      (the 33 powers are computed on the host)
+ *     sel  = max_o Qt(s')[o];  double_dqn != 0:  sel = Qt(s')[first argmax_o Q(s')[o]]  (strict >: the first maximum wins)
+ *     G    = r[i] + (disc * cont) * sel
+ *     d    = Q(s)[a[i]] - G;   e = |d|
+ *     l    = e < delta ? (e * e) * 0.5 : delta * (e - 0.5 * delta)
+ *     gi   = (e < delta ? d : sign(d) * delta) / (float)batch;   with weights:  gi *= weights[i],  l *= weights[i]
+ *     loss_out[0] = (sum_i l) / (float)batch,   td_out[i] = e (td_out nullable),   grad_out = the back-propagation of gi through Q
+ * a[i] is only ever compared (o == a[i]), never used as an index: an action outside 0 .. na - 1 cannot read or write out of bounds,
+ * and such a sample contributes gi = 0, l = 0 and td_out[i] = 0.  The bounds-checked build (build.py --variant=bounds) refuses such
+ * a batch with RLHIP_EINVAL instead (one more launch and a stream synchronisation).
+ *
+ * Summation order -- fixed, a function of (batch, h, ns, na) only; no float atomics; two calls on the same inputs give the same bytes:
+ *   layer 1     z[j] = b1[j], then fmaf(W1[j, k], x[k], .) over k ascending -- the oracle's chain, so the ReLU mask is the oracle's
+ *               bit for bit (rows are padded to a multiple of four inputs with fmaf(0, 0, z) behind the chain: z = -0 becomes +0)
+ *   Q values    lane c of a 16-lane row sums fmaf(W2[o, j], h[j], .) over j = c, c + 16, .. ascending from 0; the sixteen partial sums
+ *               meet in the xor tree (1, 2, half-row mirror, row mirror); b2[o] is added last
+ *   dh          fmaf(dq[o], W2[o, j], .) over o ascending from 0
+ *   batch sums  the batch is cut into tiles of 64 samples; workgroup g of nb = min(tiles, 256) owns tiles g, g + nb, ..
+ *               dW1, db1, dW2: ONE fmaf / add chain per element over the workgroup's samples, ascending
+ *               db2, loss: per sample slot (i mod 64) over the workgroup's tiles ascending, then the 64 slots in the xor tree
+ *               (1, 2, half-row mirror, row mirror, 16, 32)
+ *               across workgroups: the nb partial rows in four groups of ceil(nb / 4), ascending inside a group, ((g0 + g1) + g2) + g3;
+ *               the partial losses lane-strided over 64 lanes, then the shift-down tree 32, 16, .., 1 */
+int64_t rlhip_dqn_batch_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t batch);
+int32_t rlhip_dqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int32_t act, const float* params, const float* target_params,
+                                 const float* s, const int32_t* a, const float* r, const uint8_t* term, const float* s_next,
+                                 int64_t batch, float gamma, const int32_t* n_used, const float* weights, int32_t double_dqn,
+                                 float huber_delta, void* workspace, float* grad_out, float* loss_out, float* td_out,
+                                 rlhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

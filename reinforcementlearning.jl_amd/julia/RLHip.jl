@@ -814,6 +814,26 @@ function optimise_dueling!(L::HipDQNLearner, t::HipTrajectory)
     true
 end
 
+"workspace of dqn_grad_batch! in bytes (-1: a shape it refuses)"
+dqn_batch_workspace_bytes(net::HipApproximator, batch) =
+    ccall((:rlhip_dqn_batch_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, net.n_out, batch)
+
+"loss and gradient of a two-layer Q-network on a GATHERED batch of observations with 5..16 components (a frame-layout ring: `s` /
+`s_next` are the (n_in, batch) SoA buffers of gather! / gather_nstep! / sample_gather_nstep_prioritized!).  `n_used` (the transitions
+each n-step window used: discount γ^n_used[b]), `weights` (importance sampling) and `td` (|Q(s,a) - y| per sample) may be `nothing`;
+`double_dqn` selects Qt(s')[findmax(Q(s'))].  Follow with optimise!(tn, grad; clip_norm) as the record-ring forms do"
+function dqn_grad_batch!(grad::DevBuf{Float32}, loss::DevBuf{Float32}, workspace::DevBuf{UInt8}, net::HipApproximator, tn::HipTargetNetwork,
+                         s, a, r, term, s_next, batch, γ; n_used = nothing, weights = nothing, double_dqn = false, huber_delta = 1f0,
+                         td = nothing)
+    chk(ccall((:rlhip_dqn_grad_batch_f32, LIB), Int32,
+              (Int64, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+               Float32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.n_in, net.hidden, net.n_out, net.act, net.params.ptr, tn.target.ptr, s.ptr, a.ptr, r.ptr, term.ptr, s_next.ptr, batch,
+              γ, n_used === nothing ? C_NULL : n_used.ptr, weights === nothing ? C_NULL : weights.ptr, Int32(double_dqn), huber_delta,
+              workspace.ptr, grad.ptr, loss.ptr, td === nothing ? C_NULL : td.ptr, stream()))
+    grad
+end
+
 "the Double DQN form of optimise!: the draw of the plain form (same seed, same counter), fold_double!, the indexed gradient entry on
 the folded ring, then clip + Adam and the target sync through optimise!(tn, grad)"
 function optimise_double!(L::HipDQNLearner, t::HipTrajectory)
@@ -859,7 +879,13 @@ function plan!(p::HipQBasedPolicy, env::HipVecEnv)
     step = UInt32(p.explorer.step)
     p.explorer.step += 1                      # :104,:110 -- incremented on every call, before the draw
     obs = device_state(env)
-    if net.layers == 2
+    if net.layers == 2 && net.n_in > 4        # observations of 5..16 components (AcrobotRK4Env): the plan launch of csrc/dqn_batch.hip
+        chk(ccall((:rlhip_dqn_plan_obsn_f32, LIB), Int32,
+                  (Ptr{Cvoid}, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32, Ptr{Cvoid},
+                   Ptr{Cvoid}, Ptr{Cvoid}),
+                  net.params.ptr, net.n_in, net.hidden, net.n_out, net.act, obs.ptr, env.n, ϵ, p.explorer_seed,
+                  env.env_id_base, step, p.actions.ptr, p.q.ptr, stream()))
+    elseif net.layers == 2
         chk(ccall((:rlhip_dqn_plan_f32, LIB), Int32,
                   (Ptr{Cvoid}, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32, Ptr{Cvoid},
                    Ptr{Cvoid}, Ptr{Cvoid}),

@@ -324,6 +324,9 @@ _PROTOS = {
     "rlhip_dqn_grad_idx_f32": (i32, [P(Ring), i64, i64, i32, vp, vp, i64, vp, f32, f32, vp, vp, vp, vp, vp]),
     "rlhip_dqn_grad_idx_w_f32": (i32, [P(Ring), i64, i64, i32, vp, vp, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp]),
     "rlhip_dqn_plan_f32": (i32, [vp, i64, i64, i64, i32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
+    "rlhip_dqn_plan_obsn_f32": (i32, [vp, i64, i64, i64, i32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
+    "rlhip_dqn_batch_workspace_bytes": (i64, [i64, i64, i64, i64]),
+    "rlhip_dqn_grad_batch_f32": (i32, [i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
 }
 
 _STATUS = set()

@@ -386,10 +386,18 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
         # the fused vec-step steps Adam on the vector its kernels read; a dueling net trains another vector than the one they read
         raise NotImplementedError("fused DQN step: plain Q-networks only; a DuelingApproximator (dueling_params) runs on the "
                                   "per-stage loop, rlhip.run")
+    _refuse_wide_obs(net, "fused DQN step")
     a = _lib.DqnStepArgs()
     stop_condition, hook = _fused_dqn_begin(agent, env, stop_condition, hook, a)
     # the gate is should_update_ itself, on the transitions the step's push leaves
     return _fused_dqn_steps(agent, env, stop_condition, hook, "rlhip_dqn_vec_step_f32", a, a, learner.should_update_, traces.n_env)
+
+
+def _refuse_wide_obs(net, loop):
+    """the fused vec-steps read record rings (observations of 2..4 components); wider observations train on the per-stage loop"""
+    if getattr(net, "n_in", 0) > 4:
+        raise NotImplementedError(f"{loop}: observations of 2..4 components; a Q-network on {net.n_in} components (n_in > 4, e.g. "
+                                  "AcrobotRK4Env) runs on the per-stage loop, rlhip.run")
 
 
 def _fused_dqn_begin(agent, env, stop_condition, hook, a):
@@ -525,6 +533,7 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
     if learner.process_group is not None:
         raise NotImplementedError("fused folded DQN step: 1 GPU; a learner with a process group (process_group) runs on the "
                                   "per-stage loop, rlhip.run")
+    _refuse_wide_obs(net, "fused folded DQN step")
     n_step, double = int(getattr(learner, "n_step", 1)), bool(getattr(learner, "double_dqn", False))
     dueling = getattr(net, "dueling_params", None) is not None
     f = _lib.DqnFoldStepArgs()
@@ -587,6 +596,7 @@ def run_fused_dqn_prioritized(agent, env, stop_condition=None, hook=None):
     if getattr(traces, "n_step", 1) != n_step:
         raise ValueError(f"DQNLearner(n_step = {n_step}) needs CircularPrioritizedTraces(..., n_step = {n_step}): "
                          f"these traces mask windows of {getattr(traces, 'n_step', 1)}")
+    _refuse_wide_obs(net, "fused prioritized DQN step")
     dueling = getattr(net, "dueling_params", None) is not None
     p = _lib.DqnPerStepArgs()
     f = p.fold

@@ -55,6 +55,54 @@ def dqn_plan(params, ns, h, na, act, obs, eps, seed, env_id_base, step, actions=
     return actions, q_out
 
 
+MAX_WIDE_OBS = 16  # the widest observation the two-layer DQN kernels take (csrc/dqn_batch.hip); 2..4 components: csrc/dqn.hip
+
+
+def check_wide_net(net, who):
+    """the refusals for a Q-network on more than four observation components, raised before any C call"""
+    if net.n_in > MAX_WIDE_OBS:
+        raise ValueError(f"{who}: the DQN kernels take observations of up to {MAX_WIDE_OBS} Float32 components, this network has "
+                         f"n_in = {net.n_in}; images and stacked frames need a convolutional network, which this library does not have")
+    if getattr(net, "layers", 2) == 3:
+        raise NotImplementedError(f"{who}: three-layer (bf16 MFMA) networks take observations of 2..4 components; with n_in = {net.n_in} "
+                                  "use a two-layer HipApproximator / DuelingApproximator (layers = 2)")
+
+
+def dqn_plan_obsn(params, ns, h, na, act, obs, eps, seed, env_id_base, step, actions=None, q_out=None):
+    """`dqn_plan` for observations of 5..16 components (rlhip_dqn_plan_obsn_f32): byte for byte `mlp2_forward` then `eps_greedy_select`"""
+    n = obs.shape[1]
+    actions = actions if actions is not None else torch.empty(n, dtype=torch.int32, device=obs.device)
+    q_out = q_out if q_out is not None else torch.empty((na, n), dtype=torch.float32, device=obs.device)
+    call("rlhip_dqn_plan_obsn_f32", ptr(params), ns, h, na, act, ptr(obs), n, float(eps), seed, env_id_base, step,
+         ptr(actions), ptr(q_out), stream_ptr())
+    return actions, q_out
+
+
+def dqn_batch_workspace(ns, h, na, batch, device="cuda"):
+    nbytes = int(_lib.lib.rlhip_dqn_batch_workspace_bytes(ns, h, na, batch))
+    if nbytes < 0:
+        raise ValueError(f"rlhip_dqn_grad_batch_f32 takes ns 5..16, hidden a multiple of 4 and <= 256, 1..4 actions, batch >= 1; "
+                         f"got ns = {ns}, hidden = {h}, actions = {na}, batch = {batch}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def dqn_grad_batch(ns, h, na, act, params, target_params, s, a, r, term, s_next, gamma, delta=1.0, n_used=None, weights=None,
+                   double_dqn=False, workspace=None, grad=None, loss=None, td=None):
+    """loss and gradient of the two-layer Q-network on a gathered batch (s / s_next (ns, batch), as `traces.gather` returns them
+    from a frame ring) -> (grad, loss).  n_used: the transitions each n-step window used (discount gamma ** n_used[b]); weights:
+    importance-sampling weights; td (batch,): |Q(s, a) - y| per sample."""
+    dev, b = params.device, a.numel()
+    workspace = workspace if workspace is not None else dqn_batch_workspace(ns, h, na, b, dev)
+    grad = grad if grad is not None else torch.empty_like(params)
+    loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=dev)
+    if term.dtype == torch.bool:
+        term = term.view(torch.uint8)
+    call("rlhip_dqn_grad_batch_f32", ns, h, na, act, ptr(params), ptr(target_params), ptr(s), ptr(a), ptr(r), ptr(term), ptr(s_next), b,
+         gamma, None if n_used is None else ptr(n_used), None if weights is None else ptr(weights), int(bool(double_dqn)), delta,
+         ptr(workspace), ptr(grad), ptr(loss), None if td is None else ptr(td), stream_ptr())
+    return grad, loss
+
+
 def mlp3_init(ns, h, na, seed, net_id=0, device="cuda"):
     p = torch.empty(int(_lib.lib.rlhip_mlp3_nparams(ns, h, na)), dtype=torch.float32, device=device)
     call("rlhip_mlp3_init_f32", ptr(p), ns, h, na, seed, net_id, stream_ptr())
@@ -366,8 +414,15 @@ class DQNLearner:
         self.process_group = process_group
         self.grad = torch.zeros_like(net.params)
         self.loss = torch.zeros(1, dtype=torch.float32, device=net.params.device)
-        ws = dqn_workspace if net.layers == 2 else dqn3_workspace
+        # observations of more than four components live in a frame ring: the update runs the same stages on a gathered batch
+        # (`_update_batch_`, csrc/dqn_batch.hip)
+        if self._wide:
+            check_wide_net(net, "DQNLearner")
+            ws = dqn_batch_workspace
+        else:
+            ws = dqn_workspace if net.layers == 2 else dqn3_workspace
         self.workspace = ws(net.n_in, net.hidden, net.n_out, batchsize, net.params.device)
+        self._batch = None  # the gathered batch of the last update on a frame ring (scratch)
         dev = net.params.device
         self.td = torch.zeros(batchsize, dtype=torch.float32, device=dev)
         self.is_weights = torch.ones(batchsize, dtype=torch.float32, device=dev)
@@ -375,6 +430,11 @@ class DQNLearner:
 
     def forward(self, x):
         return self.approximator.forward(x)
+
+    @property
+    def _wide(self):
+        """observations of more than four components (a property: a checkpoint holds the network, not this)"""
+        return getattr(getattr(self.approximator, "network", None), "n_in", 0) > 4
 
     def should_update_(self, trajectory, n_transitions=None):
         """the gate of optimise!: warm-up, every `update_freq`-th vec-step, the trajectory's sample / insert controller.
@@ -388,6 +448,9 @@ class DQNLearner:
     def optimise_(self, trajectory):
         traces = trajectory.container
         prioritized = hasattr(traces, "sample_prioritized")
+        batch_form = self._wide or not getattr(traces, "records_layout", True)
+        if batch_form:
+            self._check_batch_form(traces, prioritized)
         if self._nstep is not None and len(traces) < self.n_step:
             # not one full window yet: the vec-step counts, the controller is not asked (no sample is drawn; over prioritized
             # traces the masked tree has no mass yet)
@@ -398,7 +461,56 @@ class DQNLearner:
                              f"these traces mask windows of {getattr(traces, 'n_step', 1)}")
         if not self.should_update_(trajectory):
             return False
+        if batch_form:
+            return self._update_batch_(traces, prioritized)
         return self._update_(traces, prioritized)
+
+    def _check_batch_form(self, traces, prioritized):
+        """what the update on a gathered batch takes: a frame ring of Float32 observations with the network's 5..16 components,
+        uniform, or prioritized through CircularPrioritizedFrameTraces masked for this learner's n_step.  Raised before any C call."""
+        net = self.approximator.network
+        if traces.dtype != torch.float32:
+            raise NotImplementedError("DQNLearner: UInt8 frames (and stacks of them, n_stack) need a convolutional Q-network, which this "
+                                      "library does not have; NStepBatchSampler / BatchSampler serve such rings to a learner of your own")
+        if traces.obs_dim > MAX_WIDE_OBS:
+            raise ValueError(f"DQNLearner: observations of up to {MAX_WIDE_OBS} Float32 components, these traces have obs_dim = "
+                             f"{traces.obs_dim}")
+        if traces.obs_dim != net.n_in:
+            raise ValueError(f"DQNLearner: the traces hold observations of {traces.obs_dim} components, the network takes {net.n_in}")
+        if prioritized:
+            from .trajectory import CircularPrioritizedFrameTraces
+
+            if not isinstance(traces, CircularPrioritizedFrameTraces):
+                raise NotImplementedError("DQNLearner: prioritized replay of observations wider than four components takes "
+                                          "CircularPrioritizedFrameTraces(..., n_step = n_step)")
+            if traces.n_step != self.n_step:
+                raise ValueError(f"DQNLearner(n_step = {self.n_step}) needs CircularPrioritizedFrameTraces(..., n_step = {self.n_step}): "
+                                 f"these traces mask windows of {traces.n_step}")
+
+    def _update_batch_(self, traces, prioritized):
+        """`_update_` on a frame ring: the same stages, each on the batch form -- draw + gather by sampler, importance-sampling
+        weights, gradient (rlhip_dqn_grad_batch_f32: Double DQN and the per-sample discount gamma ** n_used are part of its target
+        line), priority write-back under the drawn keys, exchange and apply"""
+        b, n = self.batchsize, self.n_step
+        if prioritized:  # draw + (n-step) gather in one launch; n = 1 is the plain transition with n_used = 1
+            (self._idx, self._key, self._prio), batch = traces.sample_gather_nstep_prioritized(b, n, self.gamma, self.seed, self.draw_ctr)
+        elif self._nstep is not None:
+            self._idx = self._nstep.sample_indices(traces, self.draw_ctr)
+            batch = traces.gather_nstep(self._idx, n, self.gamma)
+        else:  # the Philox draw the record-ring gradient launch evaluates inline
+            self._idx = traces.sample_indices(b, self.seed, self.draw_ctr)
+            batch = traces.gather(self._idx) + (None,)
+        self._batch = _Scratch(batch)
+        s, a, r, t, sn, n_used = batch
+        weights = self._is_weights_() if prioritized else None
+        tn = self.approximator
+        net = tn.network
+        dqn_grad_batch(net.n_in, net.hidden, net.n_out, net.act, net.params, tn.target, s, a, r, t, sn, self.gamma, self.delta, n_used,
+                       weights, self.double_dqn, self.workspace, self.grad, self.loss, self.td)
+        if prioritized:
+            call("rlhip_per_priority_f32", ptr(self.td), b, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
+            traces.set_priority_(self._key, self.td)
+        return self._exchange_and_apply_()
 
     def _update_(self, traces, prioritized):
         """one update behind the gate, the same stages for every form: draw, importance-sampling weights, Double DQN fold, gradient,
@@ -515,6 +627,9 @@ class QBasedPolicy:
     def plan_(self, env):
         net = self.learner.approximator.network
         ex = self.explorer
+        wide = net.n_in > 4  # observations of 5..16 components: the plan launch of csrc/dqn_batch.hip
+        if wide:
+            check_wide_net(net, "QBasedPolicy")
         if ex.is_break_tie:  # tie-break variant: unfused path (forward, then the selection kernel)
             return ex.plan_(net.forward(env.state()), env_id_base=env.env_id_base)
         eps = ex.get_eps()
@@ -524,6 +639,9 @@ class QBasedPolicy:
             self._actions, self._q = dqn3_plan(net.params, net.packed, net.n_in, net.hidden, net.n_out, net.act,
                                                env.state(), eps, ex.seed, env.env_id_base, step, self._actions,
                                                self._q)
+        elif wide:
+            self._actions, self._q = dqn_plan_obsn(net.params, net.n_in, net.hidden, net.n_out, net.act, env.state(), eps,
+                                                   ex.seed, env.env_id_base, step, self._actions, self._q)
         else:
             self._actions, self._q = dqn_plan(net.params, net.n_in, net.hidden, net.n_out, net.act, env.state(), eps,
                                               ex.seed, env.env_id_base, step, self._actions, self._q)
