@@ -1367,6 +1367,98 @@ int32_t rlhip_dqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int32_t act,
                                  float huber_delta, void* workspace, float* grad_out, float* loss_out, float* td_out,
                                  rlhip_stream_t stream);
 
+/* ------------------------------------------------------------- Soft Actor-Critic (SAC) -- */
+/* (csrc/sac.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The reference calls SoftGaussianNetwork "mainly used for SAC" (RLCore/src/utils/networks.jl:127-128) and its docs name SACPolicy on
+ * Pendulum as the continuous off-policy baseline, but the Zoo's SACPolicy is not in the reference snapshot: parity with it is
+ * unpinned, and THIS TEXT is the specification (tests/sac_ref.py replays it and differentiates it independently).
+ *
+ * Scope: record rings (Float32 observations, obs_dim = ns in 2..4), ONE action component, two-layer Float32 networks with h a
+ * multiple of 4 and <= 256, act 0 relu / 1 tanh.  A frame ring, another obs_dim, h or act, batch < 1, an empty ring or a NULL array
+ * that is not nullable is RLHIP_EINVAL before any launch.  All arithmetic is Float32 without contraction; fmaf only where written.
+ *
+ * Networks, flat as rlhip_mlp2_nparams / rlhip_mlp2_init_f32 lay them out:
+ *     actor    = mlp2(ns, h, 2): pre = Dense(ns, h, act), mu = Dense(h, 1), sigma = Dense(h, 1, softplus) in one vector; output
+ *                row 0 is mu, row 1 is rho (sigma before its softplus)
+ *     critics  = [Q1 | Q2], each mlp2(ns + 1, h, 1) on vcat(s, u): input rows 0 .. ns - 1 the state, row ns the action
+ *     targets  = a copy of the critics' vector           (init net_ids: 0 actor, 1 and 2 the critics)
+ * EVERY forward pass is the chain of rlhip_mlp2_forward_f32: z[j] = b1[j], fmaf(W1[j, k], x[k], .) over k ascending; out[o] = b2[o],
+ * fmaf(W2[o, j], act(z[j]), .) over j ascending -- one lane per (sample, network), no sum crosses lanes.
+ *
+ * Actor head (HeadLogp<1> of csrc/heads.hip at d = 1; softplus_nnlib, clampj, normal_draw, normlogpdf1 of csrc/head_device.h and
+ * csrc/ppo_sample_device.h):
+ *     raw  = softplus_nnlib(rho);  sg = clampj(raw, min_sigma, max_sigma);  pass = !(raw > max_sigma) && !(raw < min_sigma)
+ *     z    = mu + sg * eps;        a  = tanhf(z);   u = action_scale * a
+ *     logp = normlogpdf1(mu, sg, z) - 2.0f * ((0.6931472f - z) - softplus_nnlib(-2.0f * z))
+ *
+ * rlhip_sac_plan_f32 -- plan! for n envs in one launch, one lane per env.  obs SoA (ns x n); eps = normal_draw(seed, env_id_base + i,
+ * step, 0); action_out[i] = u.  Nullable: logp_out, mu_out, rho_out, raw_sigma_out (n each).  mu_out / rho_out are byte for byte
+ * rlhip_mlp2_forward_f32, action_out / action_scale and logp_out byte for byte rlhip_gaussian_head_sample_f32(soft = 1) on them.
+ * deterministic != 0: u = action_scale * tanhf(mu), no draw, and logp_out must be NULL (RLHIP_EINVAL otherwise).  n = 0 is a no-op.
+ *
+ * rlhip_sac_critic_grad_f32 -- idx[i]: flat logical indices into the ring as in rlhip_dqn_grad_idx_f32 (the bounds-checked build
+ * validates them first); the record is {s, a, r, t, s'}, its action word read as the Float32 whose bits it holds (what
+ * rlhip_ring_push_transition stores when it is handed a Float32 action array).  alpha: device f32[1].  Per sample i:
+ *     eps' = normal_draw(seed, i, step, 0)                                    (the id is the batch position i)
+ *     u', logp' = the actor head at s';   x' = vcat(s', u')
+ *     qt   = Qt2(x') < Qt1(x') ? Qt2(x') : Qt1(x')
+ *     cont = t ? 0 : 1
+ *     y    = r + (gamma * cont) * (qt - alpha * logp')
+ *     x = vcat(s, a);  for c = 1, 2:  d_c = Q_c(x) - y;  l_c = d_c * d_c;  g_c = (2.0f * d_c) / (float)batch
+ *     loss_out[c - 1] = (sum_i l_c) / (float)batch                           (Flux.Losses.mse; loss_out is f32[2])
+ *     grad_out = [back-propagation of g_1 through Q1 | of g_2 through Q2]    (y is a constant; 2 mlp2_nparams(ns + 1, h, 1) floats)
+ *     y_out (nullable) f32[batch]
+ * Back-propagation of g through a critic, per sample and hidden unit j (hv = act(z[j]), act' = hv > 0 ? 1 : 0 for relu, 1 - hv hv
+ * for tanh):  dW2[j] += fmaf(g, hv, .);  dz = (g * W2[j]) * act';  db1[j] += dz;  dW1[j, k] = fmaf(dz, x[k], .);  db2 += g.
+ *
+ * rlhip_sac_actor_grad_f32 -- `critics` are the ones the critic update has already stepped (the Zoo's order).  Per sample i:
+ *     eps = normal_draw(seed, i, step, 1);  u, logp = the actor head at s;  x = vcat(s, u)
+ *     sel = Q2(x) < Q1(x) ? 2 : 1;   q = Q_sel(x)
+ *     l_i = alpha * logp - q;   stats_out = { (sum l_i) / fb, (sum q) / fb, (sum logp) / fb },  fb = (float)batch
+ *     dlogp = alpha / fb;   dq = -1.0f / fb
+ *     du   = 0, then over j ascending  fmaf((dq * W2_sel[j]) * act'(z_sel[j]), W1_sel[j, ns], du)    (the critics get no gradient)
+ *     dact = action_scale * du
+ *     (dmu, dsg) = the soft = 1 formulas of rlhip_gaussian_head_sample_bwd_f32 at d = 1, K = 1 with (dact, dlogp), the regenerated eps:
+ *         s = sg + 1.0e-8f;  zz = (z - mu) / s;  w = zz / s;  dz = dlogp (2.0f a - w);  dz = dz + dact (1.0f - a a)
+ *         dmu = dlogp w + dz;   dsg = dlogp ((zz zz - 1.0f) / s) + dz eps
+ *     draw = pass ? dsg : +0.0f                                               (a select, never a product)
+ *     drho = draw * (1.0f / (1.0f + expf(-rho)))
+ *     grad_out = back-propagation of (dmu, drho) through the actor: dW2[o, j] = fmaf(d_o, hv, .);  dh = fmaf(drho, W2[1, j],
+ *                fmaf(dmu, W2[0, j], 0));  dz = dh act';  db1[j] += dz;  dW1[j, k] = fmaf(dz, s[k], .);  db2[o] += d_o
+ *     alpha step, if alpha_lr > 0 and alpha_out != NULL:  alpha_out[0] = alpha - alpha_lr * ((-stats_out[2]) - target_entropy)
+ *         (alpha_out may be the pointer alpha: the gradient launch has read alpha before the fold writes it)
+ *     sel_out (nullable) i32[batch],  logp_out (nullable) f32[batch]
+ *
+ * Summation order of both gradients -- fixed, a function of (batch, h, ns) only; no float atomics; two calls on the same inputs
+ * give the same bytes:
+ *   batch sums  the batch is cut into tiles of 64 samples; workgroup g of nb = min(tiles, 256) owns tiles g, g + nb, ..
+ *               every gradient element, and every loss / statistic sum: ONE fmaf / add chain from +0 over the workgroup's samples in
+ *               ascending batch position
+ *   across workgroups: the nb partial rows in four groups of ceil(nb / 4), ascending inside a group, ((g0 + g1) + g2) + g3;
+ *               the partial loss / statistic sums lane-strided over 64 lanes, then the shift-down tree 32, 16, .., 1; / (float)batch
+ * workspace: at least rlhip_sac_workspace_bytes(ns, h, batch) bytes for either call (-1 for a refused shape); no initialisation.
+ *
+ * Stream separation.  One update = rlhip_ring_sample_indices -> critic gradient -> one rlhip_adam_f32 (rlhip_clip_adam_f32) over
+ * [Q1 | Q2] -> actor gradient with the alpha step -> Adam over the actor -> rlhip_polyak_f32(targets, critics, rho = 1 - tau).  plan!
+ * draws from the NORMAL stream under `seed` with step = the vec-step counter and id = the env; the two gradient launches of an update
+ * draw under `seed + 1` with step = the update counter and id = the batch position, draw index 0 for the target action at s' and 1
+ * for the actor's action at s.  No (seed, id, step, index) is used twice, so exploration noise and update noise are independent. */
+int64_t rlhip_sac_workspace_bytes(int64_t ns, int64_t h, int64_t batch);
+int32_t rlhip_sac_plan_f32(const float* actor, int64_t ns, int64_t h, int32_t act, const float* obs, int64_t n, float min_sigma,
+                           float max_sigma, float action_scale, int32_t deterministic, uint64_t seed, uint32_t env_id_base,
+                           uint32_t step, float* action_out, float* logp_out, float* mu_out, float* rho_out, float* raw_sigma_out,
+                           rlhip_stream_t stream);
+int32_t rlhip_sac_critic_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                  const float* targets, int64_t batch, const int64_t* idx, const float* alpha, float gamma,
+                                  float min_sigma, float max_sigma, float action_scale, uint64_t seed, uint32_t step, void* workspace,
+                                  float* grad_out, float* loss_out, float* y_out, rlhip_stream_t stream);
+int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                 int64_t batch, const int64_t* idx, const float* alpha, float min_sigma, float max_sigma,
+                                 float action_scale, uint64_t seed, uint32_t step, float alpha_lr, float target_entropy,
+                                 float* alpha_out, void* workspace, float* grad_out, float* stats_out, int32_t* sel_out,
+                                 float* logp_out, rlhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2085,4 +2085,57 @@ function push_period_step!(h::HipEpisodeStats, p::HipPPOPolicy, env::HipVecEnv, 
     nothing
 end
 
+# ------------------------------------------------------------------------------------------------- Soft Actor-Critic
+# The ccalls of csrc/sac.hip (include/rlhip.h, "Soft Actor-Critic": the formulas, the summation order, the stream separation).  There is
+# no Julia run loop for SAC: these are the bindings a SACPolicy written against RLCore's stages would call, in the order
+#   rlhip_ring_sample_indices -> sac_critic_grad! -> Adam over [Q1 | Q2] -> sac_actor_grad! -> Adam over the actor -> rlhip_polyak_f32.
+# `actor` = mlp2(ns, h, 2) (row 0 mu, row 1 the pre-softplus sigma), `critics` = [Q1 | Q2], each mlp2(ns + 1, h, 1) on vcat(s, u); the
+# ring is a record ring whose action words hold Float32 bits (push the env's Float32 action array).
+
+"workspace of sac_critic_grad! / sac_actor_grad! in bytes (-1: a shape they refuse)"
+sac_workspace_bytes(ns, h, batch) = ccall((:rlhip_sac_workspace_bytes, LIB), Int64, (Int64, Int64, Int64), ns, h, batch)
+
+"plan! of a SAC actor for n envs in one launch: `action` (n) = action_scale * tanh(mu + sigma * eps); `logp`, `mu`, `rho`, `raw_sigma` may
+be `nothing`.  deterministic = true: action_scale * tanh(mu), no draw (`logp` must be `nothing`)"
+function sac_plan!(action::DevBuf{Float32}, actor::DevBuf{Float32}, ns, h, act, obs::DevBuf{Float32}, n; min_sigma = 0f0,
+                   max_sigma = Inf32, action_scale = 1f0, deterministic = false, seed = UInt64(0), env_id_base = UInt32(0),
+                   step = UInt32(0), logp = nothing, mu = nothing, rho = nothing, raw_sigma = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_sac_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Int32, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              actor.ptr, ns, h, act, obs.ptr, n, min_sigma, max_sigma, action_scale, Int32(deterministic), seed, env_id_base, step,
+              action.ptr, np(logp), np(mu), np(rho), np(raw_sigma), stream()))
+    action
+end
+
+"loss (2) and gradient of [Q1 | Q2] against the soft TD target y = r + γ (1 - t) (min Qt(s', u') - α logp') on the transitions `idx`
+(flat logical indices) of a record ring; `alpha` is a device Float32; `y` (batch) may be `nothing`"
+function sac_critic_grad!(grad::DevBuf{Float32}, loss::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                          actor::DevBuf{Float32}, critics::DevBuf{Float32}, targets::DevBuf{Float32}, batch, idx, alpha::DevBuf{Float32}, γ;
+                          min_sigma = 0f0, max_sigma = Inf32, action_scale = 1f0, seed = UInt64(0), step = UInt32(0), y = nothing)
+    chk(ccall((:rlhip_sac_critic_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Float32,
+               Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, targets.ptr, batch, idx.ptr, alpha.ptr, γ, min_sigma, max_sigma, action_scale, seed,
+              step, workspace.ptr, grad.ptr, loss.ptr, y === nothing ? C_NULL : y.ptr, stream()))
+    grad
+end
+
+"gradient of the actor loss mean(α logp - min(Q1, Q2)(s, u)) against the critics the critic step has already moved, its statistics
+`stats` (loss, mean q, mean logp) and -- with alpha_lr > 0 and `alpha_out` (which may be `alpha`) -- the step of the entropy coefficient
+α - alpha_lr (-mean logp - target_entropy); `sel` (Int32, batch) and `logp` (batch) may be `nothing`"
+function sac_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                         actor::DevBuf{Float32}, critics::DevBuf{Float32}, batch, idx, alpha::DevBuf{Float32}; min_sigma = 0f0,
+                         max_sigma = Inf32, action_scale = 1f0, seed = UInt64(0), step = UInt32(0), alpha_lr = 0f0,
+                         target_entropy = -1f0, alpha_out = nothing, sel = nothing, logp = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_sac_actor_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Float32, UInt64, UInt32,
+               Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, batch, idx.ptr, alpha.ptr, min_sigma, max_sigma, action_scale, seed, step, alpha_lr,
+              target_entropy, np(alpha_out), workspace.ptr, grad.ptr, stats.ptr, np(sel), np(logp), stream()))
+    grad
+end
+
 end # module

@@ -18,6 +18,7 @@ from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint, state
 from .timing import disable_debug_timings, enable_debug_timings, timer  # noqa: F401
 from .heads import CategoricalNetwork, CovGaussianNetwork, GaussianNetwork, SoftGaussianNetwork  # noqa: F401
 from .ppo import PPOPolicy, PPOTrajectory, make_ppo_cfg  # noqa: F401
+from .sac import SACPolicy  # noqa: F401
 from .trajectory import (BatchSampler, CircularArraySARTSTraces, CircularPrioritizedFrameTraces, CircularPrioritizedTraces,  # noqa: F401
                          DoubleTargetFold, NStepBatchSampler, InsertSampleRatioController, Trajectory)
 

@@ -9,6 +9,8 @@ storage with its head / length fields, sum-tree priorities and the `n_step` of t
 loaded into: CircularPrioritizedTraces refuses a value its ring cannot serve) -- which is what JLD2 (or np.savez) stores as is.
 A DuelingApproximator adds its trained vector and a dueling TargetNetwork its target (`.../dueling_params`,
 `.../target_dueling`, beside the effective `.../params` and `.../target` the kernels read; moments have the dueling length).
+A SACPolicy is walked like any other object: `actor`, `critics`, `targets`, both Adam states (`actor_opt/...`, `critic_opt/...`), `alpha`
+and the three counters (`plan_steps`, `vec_steps`, `n_updates`); its workspace and the indices of the last update are scratch.
 `load_state_dict(obj, d)` copies it back IN PLACE (device pointers, captured graphs and C structs stay valid), after
 which the run continues bit-identically (tests/test_gpu_run.py).  Device <-> host copies go through torch here; the
 Julia glue uses rlhip_memcpy_d2h / rlhip_memcpy_h2d of the C ABI on the same buffers."""

@@ -366,6 +366,12 @@ def run(policy, env, stop_condition=None, hook=None):
     return hook
 
 
+def _refuse_sac(policy, loop):
+    """the fused vec-steps are DQN's: a SACPolicy runs on the per-stage loop"""
+    if type(policy).__name__ == "SACPolicy":
+        raise NotImplementedError(f"{loop}: a fused vec-step for SACPolicy is out of scope; use the per-stage loop, rlhip.run")
+
+
 def run_fused_dqn(agent, env, stop_condition=None, hook=None):
     """`run(agent, env, stop, hook)` for Agent{QBasedPolicy{DQNLearner}} on a HipVecEnv with the whole loop body
     (plan! -> act! -> push! -> optimise!) as ONE C-ABI call per vec-step (rlhip_dqn_vec_step_f32).  Same kernels,
@@ -374,6 +380,7 @@ def run_fused_dqn(agent, env, stop_condition=None, hook=None):
     from . import _lib
 
     policy, traj = agent.policy, agent.trajectory
+    _refuse_sac(policy, "run_fused_dqn")
     learner, ex = policy.learner, policy.explorer
     tn = learner.approximator
     net = tn.network
@@ -517,6 +524,7 @@ def run_fused_dqn_folded(agent, env, stop_condition=None, hook=None):
     from .ops import ptr
 
     policy, traj = agent.policy, agent.trajectory
+    _refuse_sac(policy, "run_fused_dqn_folded")
     learner, ex = policy.learner, policy.explorer
     tn = learner.approximator
     net = tn.network
@@ -576,6 +584,7 @@ def run_fused_dqn_prioritized(agent, env, stop_condition=None, hook=None):
     from .ops import ptr
 
     policy, traj = agent.policy, agent.trajectory
+    _refuse_sac(policy, "run_fused_dqn_prioritized")
     learner, ex = policy.learner, policy.explorer
     tn = learner.approximator
     net = tn.network

@@ -17,11 +17,18 @@ from .ops import ptr, stream_ptr
 
 class CircularArraySARTSTraces:
     """CircularArraySARTSTraces(; capacity, state = T => (obs_dim, n_env), action = Int => (n_env,),
-    reward = Float32 => (n_env,), terminal = Bool => (n_env,)).  One frame = one vec-step."""
+    reward = Float32 => (n_env,), terminal = Bool => (n_env,)).  One frame = one vec-step.
 
-    def __init__(self, capacity, n_env=1, obs_dim=1, dtype=torch.float32, device="cuda"):
+    action_dtype = torch.float32 is `action = Float32 => (n_env,)`, the traces of a continuous env with one action component (SACPolicy):
+    the action word of every transition holds the bits of a Float32 -- the push stores whatever 4-byte words it is handed -- and
+    `.action` / `gather` hand them back as Float32, reinterpreted from the same bytes."""
+
+    def __init__(self, capacity, n_env=1, obs_dim=1, dtype=torch.float32, device="cuda", action_dtype=torch.int32):
         if dtype not in (torch.float32, torch.uint8):
             raise TypeError("state eltype must be Float32 or UInt8")
+        if action_dtype not in (torch.int32, torch.float32):
+            raise TypeError("action eltype must be Int32 or Float32")
+        self.action_dtype = action_dtype
         dev = torch.device(device)
         self.capacity, self.n_env, self.obs_dim, self.dtype = capacity, n_env, obs_dim, dtype
         # Float32 observations with <= 4 components live in a RECORD ring (csrc/ring_device.h, include/rlhip.h RLHIP_RING_RECORDS):
@@ -38,7 +45,7 @@ class CircularArraySARTSTraces:
             call("rlhip_ring_init", C.byref(self.rb), capacity, n_env, obs_dim, 4, ptr(self.records), None, None, None)
         else:
             self.state = torch.zeros((capacity + 1, obs_dim, n_env), dtype=dtype, device=dev)
-            self.action = torch.zeros((capacity, n_env), dtype=torch.int32, device=dev)
+            self.action = torch.zeros((capacity, n_env), dtype=action_dtype, device=dev)
             self.reward = torch.zeros((capacity, n_env), dtype=torch.float32, device=dev)
             self.terminal = torch.zeros((capacity, n_env), dtype=torch.uint8, device=dev)
             call("rlhip_ring_init", C.byref(self.rb), capacity, n_env, obs_dim, 4 if dtype == torch.float32 else 1,
@@ -55,7 +62,8 @@ class CircularArraySARTSTraces:
             if name == "next_state":
                 return rec[:, :, 8:8 + self.obs_dim]     # s' of the transition that leaves the slot's state
             if name == "action":
-                return rec.view(torch.int32)[:, :, 4]    # (capacity + 1, n_env), by the slot of the transition's s
+                # (capacity + 1, n_env), by the slot of the transition's s; the same word as Int32 or as Float32
+                return rec[:, :, 4] if self.__dict__.get("action_dtype") == torch.float32 else rec.view(torch.int32)[:, :, 4]
             if name == "reward":
                 return rec[:, :, 5]
             return rec.view(torch.uint8)[:, :, 24]       # low byte of the terminal word (byte 24 of the 64-byte record)
@@ -66,9 +74,12 @@ class CircularArraySARTSTraces:
         call("rlhip_ring_push_state", C.byref(self.rb), ptr(obs), stream_ptr())
 
     def push_transition_(self, next_obs, action0, reward, terminal):
-        """push!(traces, (state = s', action = a, reward = r, terminal = t)); action0 is 0-based int32."""
+        """push!(traces, (state = s', action = a, reward = r, terminal = t)); action0 is 0-based int32 (Float32 with
+        action_dtype = torch.float32)."""
         if terminal.dtype == torch.bool:
             terminal = terminal.view(torch.uint8)
+        if self.action_dtype == torch.float32 and action0.dtype != torch.float32:
+            raise TypeError(f"these traces store Float32 actions, the push hands over {action0.dtype}")
         call("rlhip_ring_push_transition", C.byref(self.rb), ptr(next_obs), ptr(action0), ptr(reward),
              ptr(terminal), stream_ptr())
 
@@ -102,7 +113,7 @@ class CircularArraySARTSTraces:
         t = torch.empty(b, dtype=torch.uint8, device=dev)
         call("rlhip_ring_gather", C.byref(self.rb), ptr(idx), b, ptr(s), ptr(a), ptr(r), ptr(t), ptr(sn),
              stream_ptr())
-        return s, a, r, t, sn
+        return s, a.view(self.action_dtype), r, t, sn
 
 
 def _gather_stacked(self, idx, n_stack):
