@@ -1459,6 +1459,81 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
                                  float* alpha_out, void* workspace, float* grad_out, float* stats_out, int32_t* sel_out,
                                  float* logp_out, rlhip_stream_t stream);
 
+/* ------------------------------------------ categorical (C51) distributional DQN learner -- */
+/* (csrc/c51.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The reference's design blog names C51 and IQN as the distributional members of the QBasedPolicy family ("the estimation is not the
+ * Q-values directly. But we can still fit them into the QBasedPolicy. The main change is to override ... plan! ... to use the Q value
+ * distribution"), but the Zoo's RainbowLearner is not in the reference snapshot: parity with it is unpinned, and THIS TEXT is the
+ * specification (tests/c51_ref.py replays it in Float32 and differentiates the mathematics independently in Float64).
+ *
+ * Network: the two-layer Float32 layout mlp2(ns, h, M) of rlhip_mlp2_nparams / rlhip_mlp2_init_f32 with M = na * n_atoms output rows;
+ * row m = k + n_atoms * o holds atom k of action o (the column-major reshape (n_atoms, na, batch) of the Zoo).
+ * Envelope: ns 2..16, h a multiple of 4 and <= 256, na 1..4, n_atoms 2..64, act 0 relu / 1 tanh, v_min < v_max both finite; anything
+ * else (and a NULL array that is not nullable, n < 0, batch < 1) is RLHIP_EINVAL before any launch.
+ *
+ * All arithmetic is Float32 without contraction; fmaf only where written; "sum (k ascending)" is a chain of adds from +0.
+ *     Delta  = (v_max - v_min) / (float)(n_atoms - 1)                         (host, once)
+ *     z_k    = fmaf((float)k, Delta, v_min)
+ *     hid[j] = act(zz),  zz = b1[j], then fmaf(W1[j, k], x[k], .) over k ascending
+ *     l[m]   = b2[m], then fmaf(W2[m, j], hid[j], .) over j ascending         (one chain per logit, no sum crosses lanes)
+ *     per action o:  mx = max_k l[k, o];  e_k = expf(l[k, o] - mx);  S = sum_k e_k (k ascending)
+ *                    p[k, o] = e_k / S;   Q[o] = 0, then fmaf(z_k, p[k, o], .) over k ascending from 0
+ *
+ * rlhip_c51_forward_f32 -- forward(learner, s) for n observations, obs SoA (ns x n): q_out SoA (na x n); nullable probs_out and
+ * logits_out, SoA ((n_atoms * na) x n) in row order m.  n = 0 is a no-op.
+ * rlhip_c51_plan_f32 -- plan! in one launch: q_out (nullable) is byte for byte rlhip_c51_forward_f32 (the same kernel and the same
+ * device function from logits to Q), `actions` byte for byte rlhip_eps_greedy_select_f32 (no mask, no tie-break) on those values with
+ * the same (eps, seed, env_id_base, step).
+ *
+ * rlhip_c51_grad_batch_f32 -- loss and flat gradient on a GATHERED batch, exactly the arrays rlhip_dqn_grad_batch_f32 takes: s / s_next
+ * SoA (ns x batch), a / r / term (batch), nullable n_used and weights.  Per sample i (l, p, Q of the online net unless marked t):
+ *     cont = term[i] ? 0 : 1
+ *     disc = n_used ? rlhip_gamma_pow(gamma, clamp(n_used[i], 0, 32)) : gamma      (the 33 powers are computed on the host)
+ *     c    = disc * cont
+ *     a*   = first argmax_o Qt(s')[o] (strict >);   double_dqn != 0:  first argmax_o Q(s')[o]              -> sel_out (i32[batch])
+ *     pt_j = pt(s')[j, a*]
+ *     Tz_j = min(max(r[i] + c * z_j, v_min), v_max)
+ *     m_k  = 0, then fmaf(min(max(1 - |Tz_j - z_k| / Delta, 0), 1), pt_j, .) over j ascending   -> proj_out (n_atoms x batch SoA)
+ *     lp_k = (l(s)[k, a_i] - mx) - logf(S)
+ *     L_i  = -(0, then fmaf(m_k, lp_k, .) over k ascending)                                       -> ce_out (batch; UNWEIGHTED)
+ *     Sm   = sum_k m_k (k ascending)
+ *     g_k  = (p(s)[k, a_i] * Sm - m_k) / (float)batch;    with weights:  g_k *= weights[i],  L_i *= weights[i] in the loss
+ *     loss_out[0] = (sum_i L_i) / (float)batch;   grad_out = the back-propagation of g through rows k + n_atoms * a_i only
+ * The projection is the dense form (Dopamine / the Zoo's project_distribution), not the floor / ceil scatter: it has no hole where Tz
+ * falls exactly on an atom and needs no scatter.  m, a* and the target are constants of the differentiation.
+ * a[i] is only ever compared (o == a[i]), never used as an index: an action outside 0 .. na - 1 contributes nothing to the loss and the
+ * gradient, and ce_out[i] = 0 (sel_out and proj_out are still written).  The bounds-checked build (build.py --variant=bounds) refuses
+ * such a batch with RLHIP_EINVAL instead (one more launch and a stream synchronisation).
+ *
+ * Back-propagation and summation order -- fixed, a function of (batch, ns, h, na, n_atoms) only; no float atomics; two calls on the
+ * same inputs give the same bytes.  The batch is cut into tiles of 8 samples; workgroup w of nb = min(tiles, 256, max(1, 16 MiB / the bytes
+ * of one gradient row)) owns tiles w, w + nb, ..; "its samples" are the samples of those tiles in ascending batch position.  Every element below is ONE chain from +0:
+ *     dW2[m, j]  fmaf(g_k, hid(s)[j], .) over the workgroup's samples with a_i = o (m = k + n_atoms o)
+ *     db2[m]     adds of g_k over the same samples
+ *     dh[j]      per sample: 0, then fmaf(g_k, W2[k + n_atoms a_i, j], .) over k ascending
+ *     dz[j]      dh[j] * act',  act' = hid > 0 ? 1 : 0 for relu (the stored hid: both passes see one zz), 1 - hid hid for tanh
+ *     dW1[j, k]  fmaf(dz[j], s[k], .) over the workgroup's samples;   db1[j]  adds of dz[j]
+ *     loss       adds of L_i (weighted where weights are given) over the workgroup's samples
+ *   across workgroups: the nb partial rows and partial losses in ascending w, adds from +0; the loss is then divided by (float)batch.
+ * workspace: at least rlhip_c51_workspace_bytes(ns, h, na, n_atoms, batch) bytes (-1 for a refused shape); no initialisation.
+ *
+ * One update of rlhip.RainbowLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ce_out: (ce + eps)^alpha, written
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: QR-DQN and IQN, NoisyDense, a fused vec-step, a
+ * gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
+int32_t rlhip_c51_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
+                              float v_max, const float* obs, int64_t n, float* q_out, float* probs_out, float* logits_out,
+                              rlhip_stream_t stream);
+int32_t rlhip_c51_plan_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min, float v_max,
+                           const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step, int32_t* actions,
+                           float* q_out, rlhip_stream_t stream);
+int64_t rlhip_c51_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int64_t batch);
+int32_t rlhip_c51_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min, float v_max,
+                                 const float* params, const float* target_params, const float* s, const int32_t* a, const float* r,
+                                 const uint8_t* term, const float* s_next, int64_t batch, float gamma, const int32_t* n_used,
+                                 const float* weights, int32_t double_dqn, void* workspace, float* grad_out, float* loss_out,
+                                 float* ce_out, float* proj_out, int32_t* sel_out, rlhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

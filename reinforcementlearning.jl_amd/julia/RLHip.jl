@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2136,6 +2136,77 @@ function sac_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspac
               t.rb, h, act, actor.ptr, critics.ptr, batch, idx.ptr, alpha.ptr, min_sigma, max_sigma, action_scale, seed, step, alpha_lr,
               target_entropy, np(alpha_out), workspace.ptr, grad.ptr, stats.ptr, np(sel), np(logp), stream()))
     grad
+end
+
+# ------------------------------------------------------------------------------- categorical (C51) distributional DQN
+# The ccalls of csrc/c51.hip (include/rlhip.h, "categorical (C51) distributional DQN learner": formulas, roundings, summation order).
+# The network is HipApproximator(n_in, hidden, n_actions * n_atoms): output row k + n_atoms * o is atom k of action o.  The gradient
+# works on a GATHERED batch -- the (n_in, batch) SoA buffers of gather! / gather_nstep! / sample_gather_nstep_prioritized!, as
+# dqn_grad_batch! takes them -- so one update is  draw -> gather -> optimise!(L, s, a, r, term, s_next)  [-> the priority write-back of
+# L.ce under the drawn keys].
+
+"RainbowLearner(approximator = TargetNetwork(Chain(Dense(ns, h, act), Dense(h, n_actions * n_atoms))), n_actions, n_atoms, Vₘᵢₙ, Vₘₐₓ):
+the categorical cross-entropy against the projected Bellman target.  ns 2..16, h a multiple of 4 and <= 256, 1..4 actions, 2..64 atoms"
+mutable struct HipRainbowLearner <: AbstractLearner
+    approximator::HipTargetNetwork
+    n_actions::Int; n_atoms::Int; v_min::Float32; v_max::Float32
+    batchsize::Int; γ::Float32; max_grad_norm::Float32; double_dqn::Bool
+    n_updates::Int
+    grad::DevBuf{Float32}; loss::DevBuf{Float32}; ce::DevBuf{Float32}; workspace::DevBuf{UInt8}
+end
+function HipRainbowLearner(tn::HipTargetNetwork; n_actions, n_atoms = 51, v_min = -10f0, v_max = 10f0, batchsize = 32, γ = 0.99f0,
+                           max_grad_norm = 0f0, double_dqn = false)
+    net = tn.network
+    net.layers == 2 && net.dueling === nothing || throw(ArgumentError("HipRainbowLearner: a plain two-layer HipApproximator"))
+    net.n_out == n_actions * n_atoms || throw(ArgumentError("the network has $(net.n_out) output rows, n_actions * n_atoms = $(n_actions * n_atoms)"))
+    ws = ccall((:rlhip_c51_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64, Int64), net.n_in, net.hidden, n_actions, n_atoms,
+               batchsize)
+    ws >= 0 || throw(ArgumentError("the C51 kernels take obs_dim 2..16, hidden a multiple of 4 and <= 256, 1..4 actions, n_atoms 2..64"))
+    HipRainbowLearner(tn, n_actions, n_atoms, v_min, v_max, batchsize, γ, max_grad_norm, double_dqn, 0, DevBuf{Float32}(net.params.n),
+                      DevBuf{Float32}(1), DevBuf{Float32}(batchsize), DevBuf{UInt8}(ws))
+end
+
+"forward(learner, s): `q` (n_actions, n) = the expectation of every action's distribution; `probs` / `logits` ((n_atoms * n_actions), n)
+may be `nothing`"
+function forward!(q::DevBuf{Float32}, L::HipRainbowLearner, obs::DevBuf{Float32}, n; probs = nothing, logits = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_c51_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_atoms, net.act, L.v_min, L.v_max, obs.ptr, n, q.ptr,
+              probs === nothing ? C_NULL : probs.ptr, logits === nothing ? C_NULL : logits.ptr, stream()))
+    q
+end
+
+"plan! on the expectation of the distribution, one launch: byte for byte forward! followed by the EpsilonGreedyExplorer's selection
+(no tie-break).  `actions` (n) 0-based; `q` may be `nothing`"
+function plan!(actions::DevBuf{Int32}, L::HipRainbowLearner, obs::DevBuf{Float32}, n, ϵ; seed = UInt64(0), env_id_base = UInt32(0),
+               step = UInt32(0), q = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_c51_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_atoms, net.act, L.v_min, L.v_max, obs.ptr, n, ϵ, seed, env_id_base,
+              step, actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
+    actions
+end
+
+"loss, per-sample cross-entropy `L.ce` (unweighted: the priority is (ce + ϵ)^α) and gradient on a gathered batch, then clip + Adam and
+the target sync through optimise!(tn, grad).  `n_used`, `weights`, `proj` ((n_atoms, batch)) and `sel` (Int32, batch) may be `nothing`"
+function optimise!(L::HipRainbowLearner, s, a, r, term, s_next; batch = L.batchsize, γ = L.γ, n_used = nothing, weights = nothing,
+                   proj = nothing, sel = nothing)
+    tn, net = L.approximator, L.approximator.network
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_c51_grad_batch_f32, LIB), Int32,
+              (Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              net.n_in, net.hidden, L.n_actions, L.n_atoms, net.act, L.v_min, L.v_max, net.params.ptr, tn.target.ptr, s.ptr, a.ptr, r.ptr,
+              term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.workspace.ptr, L.grad.ptr, L.loss.ptr,
+              L.ce.ptr, np(proj), np(sel), stream()))
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
+    true
 end
 
 end # module

@@ -19,6 +19,7 @@ from .timing import disable_debug_timings, enable_debug_timings, timer  # noqa: 
 from .heads import CategoricalNetwork, CovGaussianNetwork, GaussianNetwork, SoftGaussianNetwork  # noqa: F401
 from .ppo import PPOPolicy, PPOTrajectory, make_ppo_cfg  # noqa: F401
 from .sac import SACPolicy  # noqa: F401
+from .c51 import RainbowLearner, c51_forward, c51_grad_batch, c51_plan, c51_workspace  # noqa: F401
 from .trajectory import (BatchSampler, CircularArraySARTSTraces, CircularPrioritizedFrameTraces, CircularPrioritizedTraces,  # noqa: F401
                          DoubleTargetFold, NStepBatchSampler, InsertSampleRatioController, Trajectory)
 

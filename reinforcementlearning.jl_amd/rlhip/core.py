@@ -370,6 +370,10 @@ def _refuse_sac(policy, loop):
     """the fused vec-steps are DQN's: a SACPolicy runs on the per-stage loop"""
     if type(policy).__name__ == "SACPolicy":
         raise NotImplementedError(f"{loop}: a fused vec-step for SACPolicy is out of scope; use the per-stage loop, rlhip.run")
+    if hasattr(getattr(policy, "learner", None), "plan_distributional_"):
+        # (the vec-step kernels plan on scalar Q-values and train on Huber(TD))
+        raise NotImplementedError(f"{loop}: a fused vec-step for RainbowLearner (a categorical value distribution per action) is out "
+                                  "of scope; use the per-stage loop, rlhip.run")
 
 
 def run_fused_dqn(agent, env, stop_condition=None, hook=None):

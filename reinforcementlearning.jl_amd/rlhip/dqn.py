@@ -491,6 +491,21 @@ class DQNLearner:
         """`_update_` on a frame ring: the same stages, each on the batch form -- draw + gather by sampler, importance-sampling
         weights, gradient (rlhip_dqn_grad_batch_f32: Double DQN and the per-sample discount gamma ** n_used are part of its target
         line), priority write-back under the drawn keys, exchange and apply"""
+        b = self.batchsize
+        s, a, r, t, sn, n_used = self._draw_batch_(traces, prioritized)
+        weights = self._is_weights_() if prioritized else None
+        tn = self.approximator
+        net = tn.network
+        dqn_grad_batch(net.n_in, net.hidden, net.n_out, net.act, net.params, tn.target, s, a, r, t, sn, self.gamma, self.delta, n_used,
+                       weights, self.double_dqn, self.workspace, self.grad, self.loss, self.td)
+        if prioritized:
+            call("rlhip_per_priority_f32", ptr(self.td), b, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
+            traces.set_priority_(self._key, self.td)
+        return self._exchange_and_apply_()
+
+    def _draw_batch_(self, traces, prioritized):
+        """the draw of the batch form on a frame ring -> (s, a, r, t, s', n_used or None), gathered; `_idx` (and `_key` / `_prio` of a
+        prioritized draw) are left on the learner, the batch in `_batch` (scratch)"""
         b, n = self.batchsize, self.n_step
         if prioritized:  # draw + (n-step) gather in one launch; n = 1 is the plain transition with n_used = 1
             (self._idx, self._key, self._prio), batch = traces.sample_gather_nstep_prioritized(b, n, self.gamma, self.seed, self.draw_ctr)
@@ -501,16 +516,7 @@ class DQNLearner:
             self._idx = traces.sample_indices(b, self.seed, self.draw_ctr)
             batch = traces.gather(self._idx) + (None,)
         self._batch = _Scratch(batch)
-        s, a, r, t, sn, n_used = batch
-        weights = self._is_weights_() if prioritized else None
-        tn = self.approximator
-        net = tn.network
-        dqn_grad_batch(net.n_in, net.hidden, net.n_out, net.act, net.params, tn.target, s, a, r, t, sn, self.gamma, self.delta, n_used,
-                       weights, self.double_dqn, self.workspace, self.grad, self.loss, self.td)
-        if prioritized:
-            call("rlhip_per_priority_f32", ptr(self.td), b, self.per_eps, self.per_alpha, ptr(self.td), stream_ptr())
-            traces.set_priority_(self._key, self.td)
-        return self._exchange_and_apply_()
+        return batch
 
     def _update_(self, traces, prioritized):
         """one update behind the gate, the same stages for every form: draw, importance-sampling weights, Double DQN fold, gradient,
@@ -630,12 +636,16 @@ class QBasedPolicy:
         wide = net.n_in > 4  # observations of 5..16 components: the plan launch of csrc/dqn_batch.hip
         if wide:
             check_wide_net(net, "QBasedPolicy")
+        dist = getattr(self.learner, "plan_distributional_", None)  # a learner whose network estimates a value DISTRIBUTION per action
         if ex.is_break_tie:  # tie-break variant: unfused path (forward, then the selection kernel)
-            return ex.plan_(net.forward(env.state()), env_id_base=env.env_id_base)
+            values = self.learner.forward(env.state()) if dist is not None else net.forward(env.state())
+            return ex.plan_(values, env_id_base=env.env_id_base)
         eps = ex.get_eps()
         step = ex.step
         ex.step += 1
-        if net.layers == 3:
+        if dist is not None:  # plan! on the expectation of the distribution, one launch (csrc/c51.hip)
+            self._actions, self._q = dist(env.state(), eps, ex.seed, env.env_id_base, step, self._actions, self._q)
+        elif net.layers == 3:
             self._actions, self._q = dqn3_plan(net.params, net.packed, net.n_in, net.hidden, net.n_out, net.act,
                                                env.state(), eps, ex.seed, env.env_id_base, step, self._actions,
                                                self._q)
