@@ -54,7 +54,8 @@ def _stale(target, deps):
 # every entry point that takes caller-supplied gather indices validates them first (rlhip_ring_check_indices; include/rlhip.h).
 # Use it with RLHIP_LIB_PATH=<...>/lib/librlhip_bounds.so (rlhip/_lib.py) or point the Julia glue's `librlhip` at it.
 VARIANTS = {"bounds": (os.path.join(HERE, "build_bounds"), os.path.join(LIBDIR, "librlhip_bounds.so"), ["-DRLHIP_BOUNDS_CHECK"]),
-            # per-phase cycle sums of the two-wave PPO rollout, printed by workgroup 0 (a profiling aid: tools/rollout_one.py)
+            # per-phase cycle sums of the two-wave PPO rollout and the stamps of its prologue / epilogue (profiles/rollout_edges.md),
+            # printed by workgroup 0 (a profiling aid: tools/rollout_one.py)
             "rollout_timing": (os.path.join(HERE, "build_rt"), os.path.join(LIBDIR, "librlhip_rt.so"), ["-DRLHIP_ROLLOUT_TIMING"])}
 
 

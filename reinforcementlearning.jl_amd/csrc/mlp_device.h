@@ -45,16 +45,19 @@ struct NetRegs {
     float b2[MAXO];
 };
 
-// lane `sub` of an L-lane group owns hidden units j = sub + L * m
-template <int NS, int HPL>
-__device__ __forceinline__ void load_net(NetRegs<NS, HPL>& r, const float* __restrict__ p, int h, int nout,
-                                         int sub, int L) {
+// lane `sub` of an L-lane group owns hidden units j = sub + L * m (the L lanes of a group read L consecutive floats of every
+// plane: one 64-byte segment per load at L = 16).  load_net_units loads the units m in [M0, M1), and with M1 == HPL the output
+// biases: a caller with work that does not need the net may put it between two halves (a wavefront has 63 loads in flight at
+// most, so the 64th of a cold parameter vector waits for the first one's whole latency before it can issue).
+template <int NS, int HPL, int M0, int M1>
+__device__ __forceinline__ void load_net_units(NetRegs<NS, HPL>& r, const float* __restrict__ p, int h, int nout,
+                                               int sub, int L) {
     const float* W1 = p;
     const float* b1 = W1 + h * NS;
     const float* W2 = b1 + h;
     const float* b2 = W2 + nout * h;
 #pragma unroll
-    for (int m = 0; m < HPL; ++m) {
+    for (int m = M0; m < M1; ++m) {
         int j = sub + L * m;
 #pragma unroll
         for (int k = 0; k < NS; ++k) r.w1[m][k] = W1[j + h * k];
@@ -62,8 +65,16 @@ __device__ __forceinline__ void load_net(NetRegs<NS, HPL>& r, const float* __res
 #pragma unroll
         for (int o = 0; o < MAXO; ++o) r.w2[m][o] = (o < nout) ? W2[o + nout * j] : 0.0f;
     }
+    if constexpr (M1 == HPL) {
 #pragma unroll
-    for (int o = 0; o < MAXO; ++o) r.b2[o] = (o < nout) ? b2[o] : 0.0f;
+        for (int o = 0; o < MAXO; ++o) r.b2[o] = (o < nout) ? b2[o] : 0.0f;
+    }
+}
+
+template <int NS, int HPL>
+__device__ __forceinline__ void load_net(NetRegs<NS, HPL>& r, const float* __restrict__ p, int h, int nout,
+                                         int sub, int L) {
+    load_net_units<NS, HPL, 0, HPL>(r, p, h, nout, sub, L);
 }
 
 // out[o] = b2[o] + sum_j W2[o,j] * act(b1[j] + sum_k W1[j,k] x[k]); partial sums per lane (ascending m),

@@ -118,6 +118,29 @@ __device__ unsigned int g_rollout_exact_waves = 0;
             printf("%s T=%d: %lld %lld %lld %lld %lld %lld %lld %lld\n", tag, T, rt_[0], rt_[1], rt_[2], rt_[3], rt_[4], \
                    rt_[5], rt_[6], rt_[7]);                                                                       \
     } while (0)
+// the launch outside its step loop (profiles/rollout_edges.md): absolute stamps of one lane per role, kept in LDS so that they
+// hold no registers across the loop; printed as ticks since kernel entry.  RT_EDGE_LANDED waits for the wave's outstanding
+// loads and stores first (what the next use, or the end of the kernel, would wait for).
+#define RT_EDGE_DECL __shared__ long long l_edge_[2][8]
+#define RT_EDGE(k)                                                                                  \
+    do {                                                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                          \
+        if ((threadIdx.x & 255) == 0) l_edge_[threadIdx.x >> 8][k] = (long long)__builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_sched_barrier(0);                                                          \
+    } while (0)
+#define RT_EDGE_LANDED(k)                                       \
+    do {                                                        \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+        RT_EDGE(k);                                             \
+    } while (0)
+#define RT_EDGE_PRINT(tag)                                                                                          \
+    do {                                                                                                            \
+        if (blockIdx.x == 0 && (threadIdx.x & 255) == 0) {                                                          \
+            const long long* e_ = l_edge_[threadIdx.x >> 8];                                                        \
+            printf("%s T=%d: %lld %lld %lld %lld %lld %lld %lld\n", tag, T, e_[1] - e_[0], e_[2] - e_[0], e_[3] - e_[0], \
+                   e_[4] - e_[0], e_[5] - e_[0], e_[6] - e_[0], e_[7] - e_[0]);                                       \
+        }                                                                                                           \
+    } while (0)
 #else
 #define RT_COUNT_EXACT()
 #define RT_PRINT_EXACT()
@@ -125,6 +148,10 @@ __device__ unsigned int g_rollout_exact_waves = 0;
 #define RT_START()
 #define RT_STAMP(k)
 #define RT_PRINT(tag)
+#define RT_EDGE_DECL
+#define RT_EDGE(k)
+#define RT_EDGE_LANDED(k)
+#define RT_EDGE_PRINT(tag)
 #endif
 
 template <class P, int H, int L, int ACT, int NOA, int HEAD>
@@ -133,6 +160,8 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
                                                                uint64_t seed, uint32_t env_id_base,
                                                                uint32_t vec_step0_in, const uint32_t* __restrict__ ctr, TrajPtrs tr,
                                                                int store_state, float select_margin) {
+    RT_EDGE_DECL;
+    RT_EDGE(0);  // kernel entry
     const uint32_t vec_step0 = vec_step0_in + (ctr ? ctr[0] : 0u);  // device-resident counter (graph replay)
     constexpr int NS = P::ODIM;
     constexpr int HPL = H / L;
@@ -157,11 +186,15 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
     __shared__ float4 l_step[2][EPB][2];
     // HEAD == 2: (a_best, d) of the last steps (L are kept), written and read by the critic wave alone
     __shared__ float2 l_lse[HEAD == 2 ? EPB : 1][NOISE_CH];
+    // {value, reward, terminal, -} of every step while T fits, written and read by the critic wave alone: the operands of the
+    // GAE + returns scan (gae_device.h; the odd slot count keeps the envs of a wavefront on different banks, slot T is padding)
+    __shared__ __attribute__((aligned(16))) float l_scan[EPB][GAE_LDS_T + 1][4];
 
     if (role == 0) {
         __builtin_amdgcn_s_setprio(3);  // the chain goes first whenever both waves of the SIMD are ready
         NetRegs<NS, HPL> A;
         load_net<NS, HPL>(A, params, H, pd.nout_a, sub, L);
+        RT_EDGE(1);  // net loads issued
         LaneState<float> e;
 #pragma unroll
         for (int k = 0; k < P::SDIM; ++k) e.s[k] = st.s[k][env];
@@ -171,7 +204,9 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
         bool last_d = false;
         [[maybe_unused]] const double sel_km = decide2_slope((double)select_margin);
         RT_DECL;
+        RT_EDGE_LANDED(2);  // net and state present
         __syncthreads();  // the noise of chunk 0
+        RT_EDGE(3);  // first barrier passed
         RT_START();
         for (int t = 0; t < T; ++t) {
             double nz[MAXO];  // requested before the forward pass, consumed after it
@@ -223,14 +258,15 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
             __syncthreads();
             RT_STAMP(5);  // barrier
         }
-        RT_PRINT("actor wave: obs/noise | forward | select | env step | record | barrier");
-        if (HEAD == 2) RT_PRINT_EXACT();
+        RT_EDGE(4);  // loop end
         {
             float x[4] = {0.f, 0.f, 0.f, 0.f};
             env_obs1(p, e, x);
             if (sub == 0) l_step[T & 1][eg][0] = make_float4(x[0], x[1], x[2], x[3]);
             __syncthreads();
         }
+        RT_EDGE(5);  // last barrier passed
+        RT_EDGE(6);
         if (writer && store_state) {
 #pragma unroll
             for (int k = 0; k < P::SDIM; ++k) st.s[k][env] = e.s[k];
@@ -241,9 +277,18 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
                 st.done[env] = (uint8_t)last_d;
             }
         }
+        RT_EDGE_LANDED(7);  // state written back
+        RT_PRINT("actor wave: obs/noise | forward | select | env step | record | barrier");
+        if (HEAD == 2) RT_PRINT_EXACT();
+        RT_EDGE_PRINT("actor wave edges: net issued | net + state present | first barrier | loop end | last barrier | = | state stored");
     } else {
+        // the critic is first needed behind the barrier of step 0, the noise of chunk 0 at the first barrier, where the actor wave
+        // waits for it: half of the net's loads go out in front of the noise (they fit the wavefront's 63 loads in flight and
+        // fly while the noise is computed), the other half behind it
         NetRegs<NS, HPL> C;
-        load_net<NS, HPL>(C, params + pd.np_a, H, 1, sub, L);
+        load_net_units<NS, HPL, 0, HPL / 2>(C, params + pd.np_a, H, 1, sub, L);
+        RT_EDGE(1);  // first half of the net loads issued
+        const bool lds_scan = T > 0 && T <= GAE_LDS_T && tr.adv && tr.ret;
         // noise of steps [c0, c0 + NOISE_CH): one step per lane of the env's group (same operations as policy_sample)
         auto fill_noise = [&](int c0) {
             for (int i = sub; i < NOISE_CH && c0 + i < T; i += L) {
@@ -256,7 +301,10 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
         };
         fill_noise(0);
         RT_DECL;
+        RT_EDGE(2);  // chunk-0 noise published
+        load_net_units<NS, HPL, HPL / 2, HPL>(C, params + pd.np_a, H, 1, sub, L);
         __syncthreads();
+        RT_EDGE(3);  // first barrier passed
         RT_START();
         for (int t = 0; t < T; ++t) {
             // the actor wave is in step t, reading chunk t / 16: the other buffer (last read in step t - 1) takes the next chunk
@@ -272,6 +320,11 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
             if constexpr (HEAD == 2) {
                 const float4 rec = l_step[t & 1][eg][1];
                 if (sub == 0) l_lse[eg][t & (NOISE_CH - 1)] = make_float2(rec.x, rec.y);
+                if (lds_scan && sub == 0) {
+                    l_scan[eg][t][0] = oc[0];
+                    l_scan[eg][t][1] = rec.w;
+                    l_scan[eg][t][2] = (__float_as_int(rec.z) >> 8) ? 1.0f : 0.0f;
+                }
                 if (writer) {
 #pragma unroll
                     for (int k = 0; k < NS; ++k) tr.obs[((int64_t)t * NS + k) * n + env] = x[k];
@@ -295,20 +348,27 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // ... before lane 0 overwrites it
                     __builtin_amdgcn_wave_barrier();
                 }
-            } else if (writer) {
+            } else {
                 const float4 rec = l_step[t & 1][eg][1];
+                if (lds_scan && sub == 0) {
+                    l_scan[eg][t][0] = oc[0];
+                    l_scan[eg][t][1] = rec.z;
+                    l_scan[eg][t][2] = rec.w != 0.0f ? 1.0f : 0.0f;
+                }
+                if (writer) {
 #pragma unroll
-                for (int k = 0; k < NS; ++k) tr.obs[((int64_t)t * NS + k) * n + env] = x[k];
-                tr.value[(int64_t)t * n + env] = oc[0];
-                tr.logp[(int64_t)t * n + env] = rec.x;
-                if (cont) tr.action_f[(int64_t)t * n + env] = rec.y;
-                else tr.action_i[(int64_t)t * n + env] = __float_as_int(rec.y);
-                tr.reward[(int64_t)t * n + env] = rec.z;
-                tr.terminal[(int64_t)t * n + env] = (uint8_t)(rec.w != 0.0f);
+                    for (int k = 0; k < NS; ++k) tr.obs[((int64_t)t * NS + k) * n + env] = x[k];
+                    tr.value[(int64_t)t * n + env] = oc[0];
+                    tr.logp[(int64_t)t * n + env] = rec.x;
+                    if (cont) tr.action_f[(int64_t)t * n + env] = rec.y;
+                    else tr.action_i[(int64_t)t * n + env] = __float_as_int(rec.y);
+                    tr.reward[(int64_t)t * n + env] = rec.z;
+                    tr.terminal[(int64_t)t * n + env] = (uint8_t)(rec.w != 0.0f);
+                }
             }
             RT_STAMP(3);  // trajectory stores issued
         }
-        RT_PRINT("critic wave: noise | barrier | forward | stores");
+        RT_EDGE(4);  // loop end
         __syncthreads();  // the state after the last step
         {
             const float4 xv = l_step[T & 1][eg][0];
@@ -320,10 +380,27 @@ __global__ __launch_bounds__(512, 1) void rollout_split_kernel(P p, EnvArrays<fl
                 for (int k = 0; k < NS; ++k) tr.obs[((int64_t)T * NS + k) * n + env] = x[k];
                 tr.value[(int64_t)T * n + env] = oc[0];
             }
+            // generalized_advantage_estimation + returns for this env.  T <= GAE_LDS_T: from the records the wave kept in LDS --
+            // the terms that do not depend on the recurrence formed by the env's L lanes side by side, one sequential chain, adv /
+            // ret stored one step per lane (gae_device.h).  Longer rollouts: from the values / rewards lane 0 just wrote.
+            if (lds_scan) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // lane sub reads what lane 0 of its group wrote
+                __builtin_amdgcn_wave_barrier();
+                gae_lds_terms<L>(l_scan[eg], T, sub, oc[0], pd.gamma, pd.lambda);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                RT_EDGE(5);  // scan operands present
+                gae_lds_chain<L>(tr.adv, tr.ret, l_scan[eg], n, T, env, sub, active);
+            } else {
+                RT_EDGE(5);  // bootstrap value formed: the scan reads its operands back
+                if (writer && T > 0 && tr.adv && tr.ret)
+                    gae_scan_lane(tr.adv, tr.ret, tr.reward, tr.value, tr.terminal, n, T, env, pd.gamma, pd.lambda);
+            }
         }
-        // generalized_advantage_estimation + returns for this env, from the values / rewards this lane just wrote
-        if (writer && T > 0 && tr.adv && tr.ret)
-            gae_scan_lane(tr.adv, tr.ret, tr.reward, tr.value, tr.terminal, n, T, env, pd.gamma, pd.lambda);
+        RT_EDGE(6);  // scan done, last store issued
+        RT_EDGE_LANDED(7);  // every store of the wave has landed
+        RT_PRINT("critic wave: noise | barrier | forward | stores");
+        RT_EDGE_PRINT("critic wave edges: net half issued | noise published | first barrier | loop end | scan operands | scan done | stores landed");
     }
 }
 
