@@ -1519,7 +1519,7 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
  * workspace: at least rlhip_c51_workspace_bytes(ns, h, na, n_atoms, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.RainbowLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ce_out: (ce + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: QR-DQN and IQN, NoisyDense, a fused vec-step, a
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: IQN, NoisyDense, a fused vec-step, a
  * gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
 int32_t rlhip_c51_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
                               float v_max, const float* obs, int64_t n, float* q_out, float* probs_out, float* logits_out,
@@ -1533,6 +1533,76 @@ int32_t rlhip_c51_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_at
                                  const uint8_t* term, const float* s_next, int64_t batch, float gamma, const int32_t* n_used,
                                  const float* weights, int32_t double_dqn, void* workspace, float* grad_out, float* loss_out,
                                  float* ce_out, float* proj_out, int32_t* sel_out, rlhip_stream_t stream);
+
+/* ---------------------------------- quantile-regression (QR-DQN) distributional DQN learner -- */
+/* (csrc/qrdqn.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The sibling of the categorical learner that needs no hand-chosen support: every action's value distribution is N quantiles at the fixed
+ * levels tau_k, fitted by the quantile-Huber loss (Dabney et al. 2018).  The Zoo's QRDQNLearner is not in the reference snapshot either:
+ * parity with it is unpinned, and THIS TEXT is the specification (tests/qrdqn_ref.py replays it in Float32 and differentiates the
+ * mathematics independently in Float64).
+ *
+ * Network: mlp2(ns, h, M) with M = na * N output rows, N = n_quantiles; row m = k + N * o holds quantile k of action o.
+ * Envelope: ns 2..16, h a multiple of 4 and <= 256, na 1..4, N 1..64, act 0 relu / 1 tanh, kappa finite and > 0; anything else (and a NULL
+ * array that is not nullable, n < 0, batch < 1) is RLHIP_EINVAL before any launch.
+ *
+ * All arithmetic is Float32 without contraction; fmaf only where written; "sum (k ascending)" is a chain of adds from +0.
+ *     hid[j], l[m]  exactly the C51 section's two chains (one fmaf chain per output row, no sum crosses lanes)
+ *     th[k, o] = l[k + N o]                                                   (no softmax)
+ *     Q[o]     = (sum_k th[k, o], k ascending) / (float)N
+ *     tau_k    = (float)(2 k + 1) / (float)(2 N)
+ *
+ * rlhip_qrdqn_forward_f32 -- forward(learner, s) for n observations, obs SoA (ns x n): q_out SoA (na x n); nullable quantiles_out, SoA
+ * ((N * na) x n) in row order m.  n = 0 is a no-op.
+ * rlhip_qrdqn_plan_f32 -- plan! in one launch: q_out (nullable) is byte for byte rlhip_qrdqn_forward_f32 (the same kernel and the same
+ * device function from rows to Q), `actions` byte for byte rlhip_eps_greedy_select_f32 (no mask, no tie-break) on those values with the
+ * same (eps, seed, env_id_base, step).
+ *
+ * rlhip_qrdqn_grad_batch_f32 -- loss and flat gradient on a GATHERED batch, exactly the arrays rlhip_c51_grad_batch_f32 takes.  Per
+ * sample i (th, Q of the online net unless marked t):
+ *     cont, disc, c   as in the C51 section (gamma, or the 33 host-computed powers indexed by clamp(n_used[i], 0, 32)); c = disc * cont
+ *     a*    = first argmax_o Qt(s')[o] (strict >);   double_dqn != 0:  first argmax_o Q(s')[o]              -> sel_out (i32[batch])
+ *     T_j   = fmaf(c, th_t(s')[j, a*], r[i])                                                                -> target_out (N x batch SoA)
+ *     per k, with th_k = th(s)[k, a_i], and per j:
+ *         u    = T_j - th_k
+ *         hub  = |u| <= kappa ? 0.5f * u * u : kappa * (|u| - 0.5f * kappa)
+ *         dhub = min(max(u, -kappa), kappa)
+ *         w    = u < 0 ? 1.0f - tau_k : tau_k
+ *     rho_k = 0, then fmaf(w, hub  / kappa, .) over j ascending
+ *     d_k   = 0, then fmaf(w, dhub / kappa, .) over j ascending
+ *     L_i   = (sum_k rho_k, k ascending) / (float)N                                                         -> ql_out (batch; UNWEIGHTED)
+ *     g_k   = -d_k / ((float)N * (float)batch)    (the divisor is ONE Float32 product);  with weights:  g_k *= weights[i],
+ *             L_i *= weights[i] in the loss
+ *     loss_out[0] = (sum_i L_i) / (float)batch;   grad_out = the back-propagation of g through rows k + N * a_i only
+ * This is rho^kappa_tau(u) = |tau - 1{u < 0}| L_kappa(u) / kappa, summed over k and averaged over j.  T, a* and the target net are
+ * constants of the differentiation.  With kappa > 0 the gradient is continuous in u: the only decisions are a* and, for relu, the sign of
+ * a layer-1 pre-activation.
+ * a[i] is only ever compared (o == a[i]), never used as an index: an action outside 0 .. na - 1 contributes nothing to the loss and the
+ * gradient, and ql_out[i] = 0 (sel_out and target_out are still written).  The bounds-checked build (build.py --variant=bounds) refuses
+ * such a batch with RLHIP_EINVAL instead (one more launch and a stream synchronisation).
+ *
+ * Back-propagation and summation order -- the C51 section's, word for word with N for n_atoms: tiles of 8 samples, workgroup w of
+ * nb = min(tiles, 256, max(1, 16 MiB / the bytes of one gradient row)) owns tiles w, w + nb, ..; dW2 / db2 / dh / dz / dW1 / db1 / loss each
+ * ONE chain from +0 over the workgroup's samples in ascending batch position (dh over k ascending); across workgroups the nb partial rows
+ * and partial losses in ascending w, adds from +0; the loss is then divided by (float)batch.  No float atomics; two calls on the same
+ * inputs give the same bytes.
+ * workspace: at least rlhip_qrdqn_workspace_bytes(ns, h, na, N, batch) bytes (-1 for a refused shape); no initialisation.
+ *
+ * One update of rlhip.QRDQNLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ql_out: (ql + eps)^alpha, written
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: IQN and FQF, kappa = 0 (the pure quantile loss, whose
+ * gradient jumps at u = 0), NoisyDense, a fused vec-step, a gather inside the gradient launch, dueling, three-layer and bf16 nets,
+ * sharded runs, UInt8 frames. */
+int32_t rlhip_qrdqn_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
+                                int64_t n, float* q_out, float* quantiles_out, rlhip_stream_t stream);
+int32_t rlhip_qrdqn_plan_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
+                             int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step, int32_t* actions, float* q_out,
+                             rlhip_stream_t stream);
+int64_t rlhip_qrdqn_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int64_t batch);
+int32_t rlhip_qrdqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, float kappa, const float* params,
+                                   const float* target_params, const float* s, const int32_t* a, const float* r, const uint8_t* term,
+                                   const float* s_next, int64_t batch, float gamma, const int32_t* n_used, const float* weights,
+                                   int32_t double_dqn, void* workspace, float* grad_out, float* loss_out, float* ql_out, float* target_out,
+                                   int32_t* sel_out, rlhip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2204,6 +2204,79 @@ function optimise!(L::HipRainbowLearner, s, a, r, term, s_next; batch = L.batchs
               net.n_in, net.hidden, L.n_actions, L.n_atoms, net.act, L.v_min, L.v_max, net.params.ptr, tn.target.ptr, s.ptr, a.ptr, r.ptr,
               term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.workspace.ptr, L.grad.ptr, L.loss.ptr,
               L.ce.ptr, np(proj), np(sel), stream()))
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
+    true
+end
+
+# ---------------------------------------------------------------------------- quantile-regression (QR-DQN) distributional DQN
+# The ccalls of csrc/qrdqn.hip (include/rlhip.h, "quantile-regression (QR-DQN) distributional DQN learner").  The network is
+# HipApproximator(n_in, hidden, n_actions * n_quantiles): output row k + n_quantiles * o is quantile k of action o.  The gradient works
+# on a GATHERED batch, as HipRainbowLearner's does: one update is  draw -> gather -> optimise!(L, s, a, r, term, s_next)  [-> the
+# priority write-back of L.ql under the drawn keys].
+
+"QRDQNLearner(approximator = TargetNetwork(Chain(Dense(ns, h, act), Dense(h, n_actions * n_quantiles))), n_actions, n_quantiles, κ):
+the quantile-Huber loss of every (target quantile, quantile) pair; no support to choose.  ns 2..16, h a multiple of 4 and <= 256,
+1..4 actions, 1..64 quantiles, κ > 0"
+mutable struct HipQRDQNLearner <: AbstractLearner
+    approximator::HipTargetNetwork
+    n_actions::Int; n_quantiles::Int; κ::Float32
+    batchsize::Int; γ::Float32; max_grad_norm::Float32; double_dqn::Bool
+    n_updates::Int
+    grad::DevBuf{Float32}; loss::DevBuf{Float32}; ql::DevBuf{Float32}; workspace::DevBuf{UInt8}
+end
+function HipQRDQNLearner(tn::HipTargetNetwork; n_actions, n_quantiles = 51, κ = 1f0, batchsize = 32, γ = 0.99f0, max_grad_norm = 0f0,
+                         double_dqn = false)
+    net = tn.network
+    net.layers == 2 && net.dueling === nothing || throw(ArgumentError("HipQRDQNLearner: a plain two-layer HipApproximator"))
+    net.n_out == n_actions * n_quantiles ||
+        throw(ArgumentError("the network has $(net.n_out) output rows, n_actions * n_quantiles = $(n_actions * n_quantiles)"))
+    isfinite(κ) && κ > 0 || throw(ArgumentError("HipQRDQNLearner: κ must be finite and > 0 (κ = 0 is out of scope)"))
+    ws = ccall((:rlhip_qrdqn_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64, Int64), net.n_in, net.hidden, n_actions,
+               n_quantiles, batchsize)
+    ws >= 0 || throw(ArgumentError("the QR-DQN kernels take obs_dim 2..16, hidden a multiple of 4 and <= 256, 1..4 actions, n_quantiles 1..64"))
+    HipQRDQNLearner(tn, n_actions, n_quantiles, κ, batchsize, γ, max_grad_norm, double_dqn, 0, DevBuf{Float32}(net.params.n),
+                    DevBuf{Float32}(1), DevBuf{Float32}(batchsize), DevBuf{UInt8}(ws))
+end
+
+"forward(learner, s): `q` (n_actions, n) = the mean of every action's quantiles; `quantiles` ((n_quantiles * n_actions), n) may be
+`nothing`"
+function forward!(q::DevBuf{Float32}, L::HipQRDQNLearner, obs::DevBuf{Float32}, n; quantiles = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_qrdqn_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_quantiles, net.act, obs.ptr, n, q.ptr,
+              quantiles === nothing ? C_NULL : quantiles.ptr, stream()))
+    q
+end
+
+"plan! on the mean of the quantiles, one launch: byte for byte forward! followed by the EpsilonGreedyExplorer's selection (no
+tie-break).  `actions` (n) 0-based; `q` may be `nothing`"
+function plan!(actions::DevBuf{Int32}, L::HipQRDQNLearner, obs::DevBuf{Float32}, n, ϵ; seed = UInt64(0), env_id_base = UInt32(0),
+               step = UInt32(0), q = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_qrdqn_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_quantiles, net.act, obs.ptr, n, ϵ, seed, env_id_base, step,
+              actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
+    actions
+end
+
+"loss, per-sample quantile-Huber loss `L.ql` (unweighted: the priority is (ql + ϵ)^α) and gradient on a gathered batch, then clip + Adam
+and the target sync through optimise!(tn, grad).  `n_used`, `weights`, `target` ((n_quantiles, batch)) and `sel` (Int32, batch) may be
+`nothing`"
+function optimise!(L::HipQRDQNLearner, s, a, r, term, s_next; batch = L.batchsize, γ = L.γ, n_used = nothing, weights = nothing,
+                   target = nothing, sel = nothing)
+    tn, net = L.approximator, L.approximator.network
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_qrdqn_grad_batch_f32, LIB), Int32,
+              (Int64, Int64, Int64, Int64, Int32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              net.n_in, net.hidden, L.n_actions, L.n_quantiles, net.act, L.κ, net.params.ptr, tn.target.ptr, s.ptr, a.ptr, r.ptr,
+              term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.workspace.ptr, L.grad.ptr, L.loss.ptr,
+              L.ql.ptr, np(target), np(sel), stream()))
     L.n_updates += 1
     optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
     true

@@ -20,6 +20,7 @@ from .heads import CategoricalNetwork, CovGaussianNetwork, GaussianNetwork, Soft
 from .ppo import PPOPolicy, PPOTrajectory, make_ppo_cfg  # noqa: F401
 from .sac import SACPolicy  # noqa: F401
 from .c51 import RainbowLearner, c51_forward, c51_grad_batch, c51_plan, c51_workspace  # noqa: F401
+from .qrdqn import QRDQNLearner, qrdqn_forward, qrdqn_grad_batch, qrdqn_plan, qrdqn_workspace  # noqa: F401
 from .trajectory import (BatchSampler, CircularArraySARTSTraces, CircularPrioritizedFrameTraces, CircularPrioritizedTraces,  # noqa: F401
                          DoubleTargetFold, NStepBatchSampler, InsertSampleRatioController, Trajectory)
 

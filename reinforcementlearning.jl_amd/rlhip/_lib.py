@@ -337,6 +337,11 @@ _PROTOS = {
     "rlhip_c51_workspace_bytes": (i64, [i64, i64, i64, i64, i64]),
     "rlhip_c51_grad_batch_f32": (i32, [i64, i64, i64, i64, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, vp, vp, vp,
                                        vp, vp, vp, vp]),
+    "rlhip_qrdqn_forward_f32": (i32, [vp, i64, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
+    "rlhip_qrdqn_plan_f32": (i32, [vp, i64, i64, i64, i64, i32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
+    "rlhip_qrdqn_workspace_bytes": (i64, [i64, i64, i64, i64, i64]),
+    "rlhip_qrdqn_grad_batch_f32": (i32, [i64, i64, i64, i64, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, vp, vp, vp,
+                                         vp, vp, vp, vp]),
 }
 
 _STATUS = set()

@@ -6,7 +6,7 @@ distribution".  The Zoo's RainbowLearner left the tree with the rest of the Zoo,
 implements it, tests/c51_ref.py replays it).  The network is the shipped two-layer layout with n_actions * n_atoms output rows,
 row k + n_atoms * o = atom k of action o.
 
-Out of scope, refused by name: QR-DQN and IQN, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
+Out of scope, refused by name: IQN, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
 heads, sharded runs (world > 1), UInt8 frames.
 """
 import torch
@@ -69,46 +69,40 @@ def c51_grad_batch(ns, h, na, n_atoms, act, v_min, v_max, params, target_params,
 
 
 # --------------------------------------------------------------------------------------- learner
-class RainbowLearner(DQNLearner):
-    """RainbowLearner(approximator = TargetNetwork(HipApproximator(ns, h, n_actions * n_atoms)), n_actions, n_atoms = 51, v_min, v_max,
-    ...): the value of every action is a categorical distribution over the atoms z_k = v_min + k (v_max - v_min) / (n_atoms - 1); the
-    loss is the cross-entropy against the projected Bellman target.  The gate, the counters and the tail of an update are DQNLearner's
-    (`should_update_`, `_draw_`, `_is_weights_`, `_exchange_and_apply_`); every update is the batch form
+class DistributionalLearner(DQNLearner):
+    """What the distributional learners (RainbowLearner, QRDQNLearner) share: the admission checks of the approximator, the state of an
+    update and the batch form
 
-        draw -> gather -> rlhip_c51_grad_batch_f32 -> [priority write-back] -> clip + Adam -> target sync
+        draw -> gather -> the learner's gradient entry (`_grad_launch_`) -> [priority write-back] -> clip + Adam -> target sync
 
-    on record rings (ns 2..4: uniform or prioritized, 1-step or n-step through the sampler's fold) and on frame rings (ns 5..16).
-    The written-back priority is (ce + per_eps)^per_alpha of the UNWEIGHTED per-sample cross-entropy."""
+    on record rings (ns 2..4) and frame rings (ns 5..16).  The gate, the counters and the tail are DQNLearner's (`should_update_`,
+    `_draw_`, `_is_weights_`, `_exchange_and_apply_`).  Messages name the learner's own type."""
 
-    def __init__(self, approximator, n_actions, n_atoms=51, v_min=-10.0, v_max=10.0, batchsize=32, gamma=0.99, min_replay_history=100,
-                 update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
-                 double_dqn=False):
+    def _check_approximator_(self, approximator, process_group, n_actions, n_rows, rows, net_doc):
+        name = type(self).__name__
         net = getattr(approximator, "network", None)
         if net is None or not hasattr(approximator, "target"):
-            raise TypeError("RainbowLearner: the approximator is a TargetNetwork(HipApproximator(ns, h, n_actions * n_atoms))")
+            raise TypeError(f"{name}: the approximator is a TargetNetwork(HipApproximator(ns, h, {net_doc}))")
         if getattr(net, "dueling_params", None) is not None:
-            raise NotImplementedError("RainbowLearner: a DuelingApproximator (dueling distributional heads) is out of scope; use a "
+            raise NotImplementedError(f"{name}: a DuelingApproximator (dueling distributional heads) is out of scope; use a "
                                       "HipApproximator")
         if getattr(net, "layers", 2) == 3:
-            raise NotImplementedError("RainbowLearner: three-layer (layers = 3, bf16 MFMA) networks are out of scope; use a two-layer "
+            raise NotImplementedError(f"{name}: three-layer (layers = 3, bf16 MFMA) networks are out of scope; use a two-layer "
                                       "HipApproximator (layers = 2)")
         if process_group is not None:
             import torch.distributed as dist
 
             if dist.get_world_size(process_group) > 1:
-                raise NotImplementedError("RainbowLearner: sharded runs (process_group with world > 1) are out of scope")
-        n_actions, n_atoms = int(n_actions), int(n_atoms)
-        if net.n_out != n_actions * n_atoms:
-            raise ValueError(f"RainbowLearner: the network has n_out = {net.n_out} output rows, n_actions * n_atoms = "
-                             f"{n_actions} * {n_atoms} = {n_actions * n_atoms}")
-        if not float(v_min) < float(v_max) or not all(map(lambda v: abs(float(v)) < float("inf"), (v_min, v_max))):
-            raise ValueError(f"RainbowLearner: the support needs finite v_min < v_max, got [{v_min}, {v_max}]")
-        if int(update_freq) < 1 or int(batchsize) < 1:
-            raise ValueError("update_freq and batchsize must be >= 1")
+                raise NotImplementedError(f"{name}: sharded runs (process_group with world > 1) are out of scope")
+        if net.n_out != n_actions * n_rows:
+            raise ValueError(f"{name}: the network has n_out = {net.n_out} output rows, n_actions * {rows} = "
+                             f"{n_actions} * {n_rows} = {n_actions * n_rows}")
+        return net
+
+    def _init_update_state_(self, approximator, batchsize, gamma, min_replay_history, update_freq, max_grad_norm, seed, process_group,
+                            per_eps, per_alpha, per_beta, n_step, double_dqn):
+        net = approximator.network
         dev = net.params.device
-        # (raises for a shape outside the kernels' envelope, before any C call that launches)
-        self.workspace = c51_workspace(net.n_in, net.hidden, n_actions, n_atoms, int(batchsize), dev)
-        self.n_actions, self.n_atoms, self.v_min, self.v_max = n_actions, n_atoms, float(v_min), float(v_max)
         self.double_dqn = bool(double_dqn)
         self.n_step = int(n_step)
         self._nstep = None
@@ -125,10 +119,66 @@ class RainbowLearner(DQNLearner):
         self.process_group = process_group
         self.grad = torch.zeros_like(net.params)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.ce = torch.zeros(self.batchsize, dtype=torch.float32, device=dev)  # the per-sample cross-entropy, then its priority
         self.is_weights = torch.ones(self.batchsize, dtype=torch.float32, device=dev)
         self._batch = None  # the gathered batch of the last update (scratch)
         self._idx = self._key = self._prio = None
+
+    def _grad_launch_(self, batch, gamma, weights):
+        """the learner's gradient entry on the gathered batch -> the (batchsize,) tensor of UNWEIGHTED per-sample losses"""
+        raise NotImplementedError
+
+    def _gradient_batch_(self, batch, gamma, prioritized, traces):
+        per_sample = self._grad_launch_(batch, gamma, self._is_weights_() if prioritized else None)
+        if prioritized:  # trajectory[:priority, keys] = (loss_i + eps)^alpha under the drawn keys, in this call: before any further push
+            call("rlhip_per_priority_f32", ptr(per_sample), self.batchsize, self.per_eps, self.per_alpha, ptr(per_sample), stream_ptr())
+            traces.set_priority_(self._key, per_sample)
+        return self._exchange_and_apply_()
+
+    def _update_batch_(self, traces, prioritized):
+        """a frame ring (ns 5..16): the three draws of DQNLearner's batch form, gathered by the sampler"""
+        return self._gradient_batch_(self._draw_batch_(traces, prioritized), self.gamma, prioritized, traces)
+
+    def _update_(self, traces, prioritized):
+        """a record ring (ns 2..4): DQNLearner's draw, then the gather of the drawn (or folded) transitions"""
+        net = self.approximator.network
+        if traces.obs_dim != net.n_in:
+            raise ValueError(f"{type(self).__name__}: the traces hold observations of {traces.obs_dim} components, the network takes "
+                             f"{net.n_in}")
+        ring, idx, gamma, _ = self._draw_(traces, prioritized)
+        if idx is None:  # (the plain DQN learner draws inside its gradient launch: the same Philox draw, made here)
+            idx = traces.sample_indices(self.batchsize, self.seed, self.draw_ctr)
+        batch = ring.gather(idx) + (None,)
+        self._batch = _Scratch(batch)
+        return self._gradient_batch_(batch, gamma, prioritized, traces)
+
+
+class RainbowLearner(DistributionalLearner):
+    """RainbowLearner(approximator = TargetNetwork(HipApproximator(ns, h, n_actions * n_atoms)), n_actions, n_atoms = 51, v_min, v_max,
+    ...): the value of every action is a categorical distribution over the atoms z_k = v_min + k (v_max - v_min) / (n_atoms - 1); the
+    loss is the cross-entropy against the projected Bellman target.  The gate, the counters and the tail of an update are DQNLearner's
+    (`should_update_`, `_draw_`, `_is_weights_`, `_exchange_and_apply_`); every update is the batch form
+
+        draw -> gather -> rlhip_c51_grad_batch_f32 -> [priority write-back] -> clip + Adam -> target sync
+
+    on record rings (ns 2..4: uniform or prioritized, 1-step or n-step through the sampler's fold) and on frame rings (ns 5..16).
+    The written-back priority is (ce + per_eps)^per_alpha of the UNWEIGHTED per-sample cross-entropy."""
+
+    def __init__(self, approximator, n_actions, n_atoms=51, v_min=-10.0, v_max=10.0, batchsize=32, gamma=0.99, min_replay_history=100,
+                 update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
+                 double_dqn=False):
+        n_actions, n_atoms = int(n_actions), int(n_atoms)
+        net = self._check_approximator_(approximator, process_group, n_actions, n_atoms, "n_atoms", "n_actions * n_atoms")
+        if not float(v_min) < float(v_max) or not all(map(lambda v: abs(float(v)) < float("inf"), (v_min, v_max))):
+            raise ValueError(f"RainbowLearner: the support needs finite v_min < v_max, got [{v_min}, {v_max}]")
+        if int(update_freq) < 1 or int(batchsize) < 1:
+            raise ValueError("update_freq and batchsize must be >= 1")
+        # (raises for a shape outside the kernels' envelope, before any C call that launches)
+        self.workspace = c51_workspace(net.n_in, net.hidden, n_actions, n_atoms, int(batchsize), net.params.device)
+        self.n_actions, self.n_atoms, self.v_min, self.v_max = n_actions, n_atoms, float(v_min), float(v_max)
+        self._init_update_state_(approximator, batchsize, gamma, min_replay_history, update_freq, max_grad_norm, seed, process_group,
+                                 per_eps, per_alpha, per_beta, n_step, double_dqn)
+        # the per-sample cross-entropy, then its priority
+        self.ce = torch.zeros(self.batchsize, dtype=torch.float32, device=net.params.device)
 
     # ------------------------------------------------------------------------------------ plan!
     def _net_args(self):
@@ -152,31 +202,11 @@ class RainbowLearner(DQNLearner):
         return c51_plan(*self._net_args(), obs, eps, seed, env_id_base, step, actions, q_out)
 
     # -------------------------------------------------------------------------------- optimise!
-    def _gradient_batch_(self, batch, gamma, prioritized, traces):
+    def _grad_launch_(self, batch, gamma, weights):
         s, a, r, t, sn, n_used = batch
-        weights = self._is_weights_() if prioritized else None
         tn = self.approximator
         net = tn.network
         ws = self.workspace if a.numel() == self.batchsize else None
         c51_grad_batch(net.n_in, net.hidden, self.n_actions, self.n_atoms, net.act, self.v_min, self.v_max, net.params, tn.target, s, a, r,
                        t, sn, gamma, n_used, weights, self.double_dqn, ws, self.grad, self.loss, self.ce)
-        if prioritized:  # trajectory[:priority, keys] = (ce + eps)^alpha under the drawn keys, in this call: before any further push
-            call("rlhip_per_priority_f32", ptr(self.ce), self.batchsize, self.per_eps, self.per_alpha, ptr(self.ce), stream_ptr())
-            traces.set_priority_(self._key, self.ce)
-        return self._exchange_and_apply_()
-
-    def _update_batch_(self, traces, prioritized):
-        """a frame ring (ns 5..16): the three draws of DQNLearner's batch form, gathered by the sampler"""
-        return self._gradient_batch_(self._draw_batch_(traces, prioritized), self.gamma, prioritized, traces)
-
-    def _update_(self, traces, prioritized):
-        """a record ring (ns 2..4): DQNLearner's draw, then the gather of the drawn (or folded) transitions"""
-        net = self.approximator.network
-        if traces.obs_dim != net.n_in:
-            raise ValueError(f"RainbowLearner: the traces hold observations of {traces.obs_dim} components, the network takes {net.n_in}")
-        ring, idx, gamma, _ = self._draw_(traces, prioritized)
-        if idx is None:  # (the plain DQN learner draws inside its gradient launch: the same Philox draw, made here)
-            idx = traces.sample_indices(self.batchsize, self.seed, self.draw_ctr)
-        batch = ring.gather(idx) + (None,)
-        self._batch = _Scratch(batch)
-        return self._gradient_batch_(batch, gamma, prioritized, traces)
+        return self.ce

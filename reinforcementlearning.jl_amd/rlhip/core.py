@@ -372,6 +372,9 @@ def _refuse_sac(policy, loop):
         raise NotImplementedError(f"{loop}: a fused vec-step for SACPolicy is out of scope; use the per-stage loop, rlhip.run")
     if hasattr(getattr(policy, "learner", None), "plan_distributional_"):
         # (the vec-step kernels plan on scalar Q-values and train on Huber(TD))
+        if type(policy.learner).__name__ == "QRDQNLearner":
+            raise NotImplementedError(f"{loop}: a fused vec-step for QRDQNLearner (quantiles of the value distribution per action) is "
+                                      "out of scope; use the per-stage loop, rlhip.run")
         raise NotImplementedError(f"{loop}: a fused vec-step for RainbowLearner (a categorical value distribution per action) is out "
                                   "of scope; use the per-stage loop, rlhip.run")
 
