@@ -1519,7 +1519,7 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
  * workspace: at least rlhip_c51_workspace_bytes(ns, h, na, n_atoms, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.RainbowLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ce_out: (ce + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: IQN, NoisyDense, a fused vec-step, a
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: NoisyDense, a fused vec-step, a
  * gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
 int32_t rlhip_c51_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
                               float v_max, const float* obs, int64_t n, float* q_out, float* probs_out, float* logits_out,
@@ -1589,7 +1589,7 @@ int32_t rlhip_c51_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_at
  * workspace: at least rlhip_qrdqn_workspace_bytes(ns, h, na, N, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.QRDQNLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ql_out: (ql + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: IQN and FQF, kappa = 0 (the pure quantile loss, whose
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: FQF, kappa = 0 (the pure quantile loss, whose
  * gradient jumps at u = 0), NoisyDense, a fused vec-step, a gather inside the gradient launch, dueling, three-layer and bf16 nets,
  * sharded runs, UInt8 frames. */
 int32_t rlhip_qrdqn_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
@@ -1603,6 +1603,93 @@ int32_t rlhip_qrdqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_
                                    const float* s_next, int64_t batch, float gamma, const int32_t* n_used, const float* weights,
                                    int32_t double_dqn, void* workspace, float* grad_out, float* loss_out, float* ql_out, float* target_out,
                                    int32_t* sel_out, rlhip_stream_t stream);
+
+/* ------------------------------------------ implicit-quantile (IQN) distributional DQN learner -- */
+/* (csrc/iqn.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The second distributional member of the QBasedPolicy family the reference's design blog names (C51 and IQN; Dabney et al. 2018,
+ * "Implicit Quantile Networks").  The quantile LEVEL is an input of the network and is drawn anew for every evaluation, so the value
+ * distribution is represented implicitly.  The Zoo's IQNLearner / ImplicitQuantileNet are not in the reference snapshot: parity with
+ * them is unpinned, and THIS TEXT is the specification (tests/iqn_ref.py states the mathematics in Float64).
+ *
+ * Network: ImplicitQuantileNet(psi = Dense(ns, h, act), phi = Dense(n_cos, h, relu), header = Dense(h, na)).  The flat Float32 vector is
+ * in Flux.destructure order, every matrix column-major as in mlp2:
+ *     W1 (h x ns) | b1 (h) | Wphi (h x n_cos) | bphi (h) | W2 (na x h) | b2 (na)        rlhip_iqn_nparams(ns, h, na, n_cos) floats
+ * rlhip_iqn_init_f32: Glorot-uniform per Dense layer ((2 u - 1) sqrt(6 / (fan_in + fan_out))), zero biases, by the rule of
+ * rlhip_mlp2_init_f32: u = u01_f32(word 0 of philox4x32_10(seed, element, 0, net_id * 4 + {0: W1, 1: Wphi, 2: W2}, 6 (INIT))).
+ * Envelope: ns 2..16, h a multiple of 32 and <= 256, na 1..4, n_cos even and 2..64, the numbers of levels N, N', K each 1..64, act 0 relu /
+ * 1 tanh for psi (phi is always relu), kappa finite and > 0; anything else (and a NULL array that is not nullable, n < 0, batch < 1) is
+ * RLHIP_EINVAL before any launch, and rlhip_iqn_workspace_bytes returns -1.
+ *
+ * All arithmetic is Float32 without contraction; fmaf only where written; "sum (ascending)" is a chain of adds from +0.  For level n of
+ * sample / env `idx`:
+ *     tau      = (float)(w >> 15) * 0x1p-17f,   w = word (n % 4) of philox4x32_10(seed, idx, n / 4, t, TAG)
+ *                (a 17-bit grid on purpose: (e + 1) * tau is then EXACT in Float32 for e + 1 <= 64)
+ *     c[e]     = cospif((float)(e + 1) * tau),  e = 0 .. n_cos - 1     (the device library's Float32 cospi -- ocml -- on the exact product)
+ *     psi[j]   = act(b1[j], then fmaf(W1[j, k], x[k], .) over k ascending)             (once per sample: it does not depend on tau)
+ *     phi[j]   = max(bphi[j], then fmaf(Wphi[j, e], c[e], .) over e ascending, 0)
+ *     m[j]     = psi[j] * phi[j]
+ *     th[o]    = b2[o], then fmaf(W2[o, j], m[j], .) over j ascending
+ *     Q[o]     = (sum over the levels of th[o], ascending) / (float)(number of levels)
+ * TAG = 9 in plan / forward with (idx, t) = (env_id_base + env, step); 10 for the online levels tau and 11 for the target levels tau' of
+ * the gradient with (idx, t) = (batch position, draw_ctr).  The tags 0..8 are the library's other streams, so no draw is used twice.
+ * (The phi chain runs on v_mfma_f32_32x32x2_f32 with bphi as the accumulator's initial value: tools/micro/mfma_f32_l1.hip pins that this
+ * is the ascending fmaf chain bit for bit.)
+ *
+ * rlhip_iqn_forward_f32 -- n observations (obs SoA, ns x n) at n_levels = K drawn levels each: q_out SoA (na x n); nullable
+ * quantiles_out, SoA ((K * na) x n), row k + K * o = level k of action o; nullable tau_out, SoA (K x n).  n = 0 is a no-op.
+ * rlhip_iqn_plan_f32 -- plan! in one launch: q_out (nullable) is byte for byte rlhip_iqn_forward_f32 with the same (seed, env_id_base,
+ * step) (the same kernel), `actions` byte for byte rlhip_eps_greedy_select_f32 (no mask, no tie-break) on those values with the same
+ * (eps, seed, env_id_base, step).
+ *
+ * rlhip_iqn_grad_batch_f32 -- loss and flat gradient on a GATHERED batch, exactly the arrays rlhip_qrdqn_grad_batch_f32 takes, plus
+ * n_cos, N = n_levels, N' = n_target_levels, seed, draw_ctr.  Per sample i (th of the online net unless marked t):
+ *     cont, disc, c   as in the C51 section; c = disc * cont
+ *     tau_n  (n < N, tag 10)  -> tau_out (N x batch SoA);    tau'_j (j < N', tag 11)  -> tau_target_out (N' x batch SoA)
+ *     a*    = first argmax_o (strict >) of the mean over the N' levels tau' of th_t(s', tau'_j)[o];  double_dqn != 0: of the online
+ *             net's th(s', tau'_j)[o] on the same tau'                                                  -> sel_out (i32[batch])
+ *     T_j   = fmaf(c, th_t(s', tau'_j)[a*], r[i])                                                       -> target_out (N' x batch SoA)
+ *     per n, with th_n = th(s, tau_n)[a_i], and per j:  u, hub, dhub exactly as in the QR-DQN section, w = u < 0 ? 1.0f - tau_n : tau_n
+ *     rho_n = 0, then fmaf(w, hub  / kappa, .) over j ascending;    d_n = 0, then fmaf(w, dhub / kappa, .) over j ascending
+ *     L_i   = (sum_n rho_n, n ascending) / (float)N'                                                    -> ql_out (batch; UNWEIGHTED)
+ *     g_n   = -d_n / ((float)N' * (float)batch)   (ONE Float32 product);  with weights:  g_n *= weights[i],  L_i *= weights[i] in the loss
+ *     loss_out[0] = (sum_i L_i) / (float)batch
+ * T, tau, tau', a* and the target net are constants of the differentiation.  a[i] is only ever compared: an action outside 0 .. na - 1
+ * contributes nothing, and ql_out[i] = 0 (sel_out, target_out and the levels are still written).
+ *
+ * Back-propagation and summation order -- fixed, a function of the shape only; no float atomics; two calls give the same bytes.  Tiles
+ * of 8 samples and the nb rule of the C51 section (np = rlhip_iqn_nparams) decide which workgroup owns which samples; "its rows" are the
+ * (sample, n) pairs of its samples, sample-major, n ascending.  Per row:  dm[j] = g_n * W2[a_i, j];  dphi[j] = phi[j] > 0 ? dm[j] * psi[j] : 0.
+ * Every element below is ONE chain from +0:
+ *     dW2[o, j]    fmaf(g_n, m[j], .) over the workgroup's rows with a_i = o;    db2[o]  adds of g_n over the same rows
+ *     dWphi[j, e]  fmaf(dphi[j], c[e], .) over the workgroup's rows;             dbphi[j]  adds of dphi[j]
+ *     dpsi[j]      per sample: fmaf(dm[j], phi[j], .) over n ascending
+ *     dz[j]        dpsi[j] * act'  (act' of the stored psi, as in the C51 section)
+ *     dW1[j, k]    fmaf(dz[j], s[k], .) over the workgroup's samples;            db1[j]  adds of dz[j]
+ *     loss         adds of L_i (weighted where weights are given) over the workgroup's samples
+ *   across workgroups: the nb partial rows and partial losses in ascending w, adds from +0; the loss is then divided by (float)batch.
+ * workspace: at least rlhip_iqn_workspace_bytes(ns, h, na, n_cos, N, N', batch) bytes; no initialisation.
+ *
+ * One update of rlhip.IQNLearner = draw -> gather -> this gradient (seed = the learner's, draw_ctr = its draw counter) ->
+ * [rlhip_per_priority_f32 on ql_out] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: FQF, kappa = 0, NoisyDense, a fused vec-step,
+ * dueling, three-layer and bf16 nets, sharded runs, UInt8 frames, the bounds-checked build's action check. */
+int64_t rlhip_iqn_nparams(int64_t ns, int64_t h, int64_t na, int64_t n_cos);
+int32_t rlhip_iqn_init_f32(float* params, int64_t ns, int64_t h, int64_t na, int64_t n_cos, uint64_t seed, uint32_t net_id,
+                           rlhip_stream_t stream);
+int32_t rlhip_iqn_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_levels, int32_t act,
+                              const float* obs, int64_t n, uint64_t seed, uint32_t env_id_base, uint32_t step, float* q_out,
+                              float* quantiles_out, float* tau_out, rlhip_stream_t stream);
+int32_t rlhip_iqn_plan_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_levels, int32_t act,
+                           const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step, int32_t* actions,
+                           float* q_out, float* tau_out, rlhip_stream_t stream);
+int64_t rlhip_iqn_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_levels, int64_t n_target_levels,
+                                  int64_t batch);
+int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_levels, int64_t n_target_levels, int32_t act,
+                                 float kappa, const float* params, const float* target_params, const float* s, const int32_t* a,
+                                 const float* r, const uint8_t* term, const float* s_next, int64_t batch, float gamma, const int32_t* n_used,
+                                 const float* weights, int32_t double_dqn, uint64_t seed, uint32_t draw_ctr, void* workspace,
+                                 float* grad_out, float* loss_out, float* ql_out, float* target_out, int32_t* sel_out, float* tau_out,
+                                 float* tau_target_out, rlhip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # layer 1 of both of its phases on the f32 MFMA since round 3 and falls under the same rule: its actor / critic pairs are
 # two scalar FMAs, not one v_pk_fma_f32.)
 NO_SLP = ["-fno-slp-vectorize", "-fno-vectorize"]  # (the loop vectorizer packs 2-trip loops over the actions the same way)
-EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP}
+# (iqn.hip, the newest MFMA source, also switches the packed f32 instructions off at the target: no pass may form them)
+NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP, "iqn.hip": NO_SLP + NO_PK}
 
 
 def sources():

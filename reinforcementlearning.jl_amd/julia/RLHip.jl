@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2277,6 +2277,98 @@ function optimise!(L::HipQRDQNLearner, s, a, r, term, s_next; batch = L.batchsiz
               net.n_in, net.hidden, L.n_actions, L.n_quantiles, net.act, L.κ, net.params.ptr, tn.target.ptr, s.ptr, a.ptr, r.ptr,
               term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.workspace.ptr, L.grad.ptr, L.loss.ptr,
               L.ql.ptr, np(target), np(sel), stream()))
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
+    true
+end
+
+# ---------------------------------------------------------------------------------------- implicit-quantile (IQN) distributional DQN
+# The ccalls of csrc/iqn.hip (include/rlhip.h, "implicit-quantile (IQN) distributional DQN learner").  The network is
+# ImplicitQuantileNet(ψ = Dense(ns, h, act), ϕ = Dense(n_cos, h, relu), header = Dense(h, n_actions)), flat in Flux.destructure order;
+# HipIQNApproximator is a HipApproximator with that vector (Adam, HipTargetNetwork and Polyak treat it as any other), only HipIQNLearner
+# evaluates it.  One update is  draw -> gather -> optimise!(L, s, a, r, term, s_next)  [-> the priority write-back of L.ql].
+
+"FluxApproximator(model = ImplicitQuantileNet(ψ, ϕ, header), optimiser = Adam(lr)) -> (approximator, n_cos)"
+function HipIQNApproximator(n_in, hidden, n_actions; n_cos = 64, act = 0, lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, seed = 0,
+                            net_id = 0)
+    np = ccall((:rlhip_iqn_nparams, LIB), Int64, (Int64, Int64, Int64, Int64), n_in, hidden, n_actions, n_cos)
+    np > 0 || throw(ArgumentError("HipIQNApproximator: positive layer sizes"))
+    p = DevBuf{Float32}(np)
+    chk(ccall((:rlhip_iqn_init_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              p.ptr, n_in, hidden, n_actions, n_cos, seed, net_id, stream()))
+    A = HipApproximator(n_in, hidden, n_actions, 2, act, p, DevBuf{Float32}(np), DevBuf{Float32}(np),
+                        to_dev!(DevBuf{Float32}(2), Float32[beta1, beta2]), DevBuf{Float32}(1), nothing, lr, beta1, beta2, eps, nothing, nothing)
+    A, n_cos
+end
+
+"IQNLearner(approximator = TargetNetwork(ImplicitQuantileNet), n_actions, N, N′, K, κ): the quantile-Huber loss between N online and N′
+target levels drawn per sample and update; plan! on the mean over K drawn levels.  ns 2..16, h a multiple of 32 and <= 256, 1..4
+actions, n_cos even and 2..64, 1..64 levels, κ > 0"
+mutable struct HipIQNLearner <: AbstractLearner
+    approximator::HipTargetNetwork
+    n_actions::Int; n_cos::Int; N::Int; N_target::Int; K::Int; κ::Float32
+    batchsize::Int; γ::Float32; max_grad_norm::Float32; double_dqn::Bool
+    seed::UInt64; draw_ctr::UInt32; n_updates::Int
+    grad::DevBuf{Float32}; loss::DevBuf{Float32}; ql::DevBuf{Float32}; workspace::DevBuf{UInt8}
+end
+function HipIQNLearner(tn::HipTargetNetwork; n_actions, n_cos = 64, N = 32, N_target = 32, K = 32, κ = 1f0, batchsize = 32, γ = 0.99f0,
+                       max_grad_norm = 0f0, double_dqn = false, seed = 0)
+    net = tn.network
+    net.layers == 2 && net.dueling === nothing || throw(ArgumentError("HipIQNLearner: the network of HipIQNApproximator"))
+    np = ccall((:rlhip_iqn_nparams, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, n_actions, n_cos)
+    net.n_out == n_actions && net.params.n == np ||
+        throw(ArgumentError("the network is not HipIQNApproximator($(net.n_in), $(net.hidden), $n_actions; n_cos = $n_cos)"))
+    isfinite(κ) && κ > 0 || throw(ArgumentError("HipIQNLearner: κ must be finite and > 0 (κ = 0 is out of scope)"))
+    ws = ccall((:rlhip_iqn_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64, Int64, Int64, Int64), net.n_in, net.hidden,
+               n_actions, n_cos, N, N_target, batchsize)
+    ws >= 0 && 1 <= K <= 64 || throw(ArgumentError("the IQN kernels take obs_dim 2..16, hidden a multiple of 32 and <= 256, 1..4 actions, " *
+                                                   "n_cos even and 2..64, 1..64 levels"))
+    HipIQNLearner(tn, n_actions, n_cos, N, N_target, K, κ, batchsize, γ, max_grad_norm, double_dqn, seed, 0, 0,
+                  DevBuf{Float32}(net.params.n), DevBuf{Float32}(1), DevBuf{Float32}(batchsize), DevBuf{UInt8}(ws))
+end
+
+"forward(learner, s): `q` (n_actions, n) = the mean over K levels drawn under (seed, env_id_base + env, step); `quantiles`
+((K * n_actions), n) and `τ` (K, n) may be `nothing`"
+function forward!(q::DevBuf{Float32}, L::HipIQNLearner, obs::DevBuf{Float32}, n; seed = L.seed, env_id_base = UInt32(0), step = UInt32(0),
+                  quantiles = nothing, τ = nothing)
+    net = L.approximator.network
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_iqn_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, UInt64, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_cos, L.K, net.act, obs.ptr, n, seed, env_id_base, step, q.ptr,
+              np(quantiles), np(τ), stream()))
+    q
+end
+
+"plan! on the mean of the K drawn quantiles, one launch: byte for byte forward! followed by the EpsilonGreedyExplorer's selection (no
+tie-break).  `actions` (n) 0-based; `q` may be `nothing`"
+function plan!(actions::DevBuf{Int32}, L::HipIQNLearner, obs::DevBuf{Float32}, n, ϵ; seed = UInt64(0), env_id_base = UInt32(0),
+               step = UInt32(0), q = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_iqn_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_cos, L.K, net.act, obs.ptr, n, ϵ, seed, env_id_base, step,
+              actions.ptr, q === nothing ? C_NULL : q.ptr, C_NULL, stream()))
+    actions
+end
+
+"loss, per-sample quantile-Huber loss `L.ql` (unweighted) and gradient on a gathered batch at levels drawn under (L.seed, batch position,
+L.draw_ctr), then clip + Adam and the target sync through optimise!(tn, grad).  `n_used`, `weights`, `target` ((N′, batch)) and `sel`
+(Int32, batch) may be `nothing`"
+function optimise!(L::HipIQNLearner, s, a, r, term, s_next; batch = L.batchsize, γ = L.γ, n_used = nothing, weights = nothing,
+                   target = nothing, sel = nothing)
+    tn, net = L.approximator, L.approximator.network
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_iqn_grad_batch_f32, LIB), Int32,
+              (Int64, Int64, Int64, Int64, Int64, Int64, Int32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.n_in, net.hidden, L.n_actions, L.n_cos, L.N, L.N_target, net.act, L.κ, net.params.ptr, tn.target.ptr, s.ptr, a.ptr,
+              r.ptr, term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.seed, L.draw_ctr, L.workspace.ptr,
+              L.grad.ptr, L.loss.ptr, L.ql.ptr, np(target), np(sel), C_NULL, C_NULL, stream()))
+    L.draw_ctr += 1
     L.n_updates += 1
     optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
     true

@@ -342,6 +342,13 @@ _PROTOS = {
     "rlhip_qrdqn_workspace_bytes": (i64, [i64, i64, i64, i64, i64]),
     "rlhip_qrdqn_grad_batch_f32": (i32, [i64, i64, i64, i64, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, vp, vp, vp,
                                          vp, vp, vp, vp]),
+    "rlhip_iqn_nparams": (i64, [i64, i64, i64, i64]),
+    "rlhip_iqn_init_f32": (i32, [vp, i64, i64, i64, i64, u64, u32, vp]),
+    "rlhip_iqn_forward_f32": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, u64, u32, u32, vp, vp, vp, vp]),
+    "rlhip_iqn_plan_f32": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, f64, u64, u32, u32, vp, vp, vp, vp]),
+    "rlhip_iqn_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64, i64]),
+    "rlhip_iqn_grad_batch_f32": (i32, [i64, i64, i64, i64, i64, i64, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, u64, u32,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _STATUS = set()

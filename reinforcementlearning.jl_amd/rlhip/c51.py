@@ -6,7 +6,7 @@ distribution".  The Zoo's RainbowLearner left the tree with the rest of the Zoo,
 implements it, tests/c51_ref.py replays it).  The network is the shipped two-layer layout with n_actions * n_atoms output rows,
 row k + n_atoms * o = atom k of action o.
 
-Out of scope, refused by name: IQN, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
+Out of scope, refused by name: NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
 heads, sharded runs (world > 1), UInt8 frames.
 """
 import torch
