@@ -1519,8 +1519,8 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
  * workspace: at least rlhip_c51_workspace_bytes(ns, h, na, n_atoms, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.RainbowLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ce_out: (ce + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: NoisyDense, a fused vec-step, a
- * gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  (NoisyDense networks: the section after IQN.)  Out of scope: a fused
+ * vec-step, a gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
 int32_t rlhip_c51_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
                               float v_max, const float* obs, int64_t n, float* q_out, float* probs_out, float* logits_out,
                               rlhip_stream_t stream);
@@ -1690,6 +1690,74 @@ int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_co
                                  const float* weights, int32_t double_dqn, uint64_t seed, uint32_t draw_ctr, void* workspace,
                                  float* grad_out, float* loss_out, float* ql_out, float* target_out, int32_t* sel_out, float* tau_out,
                                  float* tau_target_out, rlhip_stream_t stream);
+
+/* ------------------------------------------------ NoisyDense networks for the categorical learner -- */
+/* (csrc/noisy.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * NoisyNet exploration (Fortunato et al. 2018, factorised Gaussian noise), the sixth Rainbow ingredient.  NoisyDense is not in the
+ * reference snapshot (it is named in its docs only): parity is unpinned, and THIS TEXT is the specification (tests/noisy_ref.py states
+ * it in Float64).
+ *
+ * Noisy vector: [ mu | sigma ], each half laid out exactly as rlhip_mlp2_nparams(ns, h, M) lays a plain net out (W1 | b1 | W2 | b2);
+ * rlhip_noisy_nparams = 2 * rlhip_mlp2_nparams (-1 for a refused shape).
+ * Layer:  y = (Wmu + Wsg .* f(e_out) f(e_in)') x + bmu + bsg .* f(e_out),   f(e) = copysignf(sqrtf(fabsf(e)), e).
+ * rlhip_noisy_init_f32, p = the fan-in of the layer (ns for W1 and b1, h for W2 and b2):
+ *     mu    = (2.0f * u - 1.0f) / sqrtf((float)p)   (a true division), biases by the same law;
+ *             u = u01_f32(word 0 of philox4x32_10(seed, element, 0, net_id * 4 + {0: W1, 1: b1, 2: W2, 3: b2}, 6 (INIT)))
+ *     sigma = sigma0 / sqrtf((float)p)              (sigma0 finite and >= 0; rlhip.NoisyApproximator's default is 0.5)
+ * Draws:  e_q = normal_draw(seed, id, step, q) UNDER A TAG: the Float64 Box-Muller of the sampling heads -- w = philox4x32_10(seed, id,
+ * q >> 1, step, TAG), u1 = ((w.x >> 8) + 1) 2^-24, u2 = (w.y >> 8) 2^-24, r = sqrt(-2 log u1), e = (float)(r cos(2 pi u2)) for even q,
+ * (float)(r sin(2 pi u2)) for odd q -- whose bits under tag 3 (NORMAL) are unchanged.  TAG = 12 (NOISY_ACT) in forward / plan, 13
+ * (NOISY_ONLINE) and 14 (NOISY_TARGET) in the folds.  The index of a factor does not depend on the shape, and every region starts on an
+ * even index (one Philox block serves two neighbouring factors):
+ *     a[k] = f(e_q), q = k          layer-1 inputs        b[j] = f(e_q), q = 16 + j     layer-1 outputs
+ *     c[j] = f(e_q), q = 272 + j    layer-2 inputs        d[m] = f(e_q), q = 528 + m    layer-2 outputs
+ * Acting: id = env_id_base + env (wrapping, as in the other plan kernels), step = the explorer's step.  Folds: id = 0, step = counter.
+ * Envelope: the C51 envelope unchanged -- ns 2..16, h a multiple of 4 and <= 256, na 1..4, n_atoms 2..64, act 0 relu / 1 tanh, finite
+ * v_min < v_max; init / fold / unfold take the same nets by their row count n_out = M in 2..256.  Anything else (and a NULL array that
+ * is not nullable, n < 0) is RLHIP_EINVAL before any launch.
+ *
+ * rlhip_noisy_c51_forward_f32 / rlhip_noisy_c51_plan_f32 -- their C51 namesakes with an independent noise sample PER ENV (the forward
+ * form takes seed, env_id_base, step too).  All arithmetic is Float32 without contraction; fmaf only where written.  Per env:
+ *     u[k]   = a[k] * x[k]
+ *     zmu    = b1mu[j], then fmaf(W1mu[j, k], x[k], .) over k ascending
+ *     zsg    = b1sg[j], then fmaf(W1sg[j, k], u[k], .) over k ascending
+ *     hid[j] = act(fmaf(b[j], zsg, zmu))
+ *     v[j]   = c[j] * hid[j]
+ *     lmu    = b2mu[m], then fmaf(W2mu[m, j], hid[j], .) over j ascending
+ *     lsg    = b2sg[m], then fmaf(W2sg[m, j], v[j], .)   over j ascending
+ *     l[m]   = fmaf(d[m], lsg, lmu)
+ * then the C51 section's lines: per action the softmax and Q[o] = sum z_k p[k, o] (the same device function), and in the plan form
+ * `actions` byte for byte rlhip_eps_greedy_select_f32 (no mask, no tie-break) on the kernel's own q_out with the same (eps, seed,
+ * env_id_base, step).  With sigma = 0 the outputs are byte for byte rlhip_c51_forward_f32 on the mu half (fmaf(b, 0, zmu) = zmu).
+ * q_out SoA (na x n), nullable in the plan form; probs_out / logits_out nullable, SoA ((n_atoms * na) x n).  n = 0 is a no-op.  No float
+ * atomics, no sum across lanes: two calls on the same inputs give the same bytes.  rlhip_noisy_plan_tile: the envs one workgroup serves.
+ *
+ * rlhip_noisy_fold_f32 -- one noise sample for the whole net (NoisyNet-DQN's per-update sample): with xi_W[o, i] = f_out[o] * f_in[i]
+ * (ONE product; W1: b[j] * a[k], W2: d[m] * c[j]) and xi_b[o] = f_out[o],  eff = fmaf(sigma, xi, mu): a plain mlp2 vector every C51
+ * kernel takes unchanged.  The first pair draws under tag 13; the optional second pair (noisy2, eff2: both or neither) is the target
+ * net, same launch, tag 14.  eff must not overlap any input, eff2 neither eff nor any input.
+ * rlhip_noisy_unfold_grad_f32 -- the chain rule of the fold for the online net: regenerates the tag-13 draws of (seed, counter) and writes
+ * grad_noisy = [ dmu = g | dsigma = g * xi ] (xi the same single product); grad_noisy must not overlap grad_eff.
+ *
+ * One update of rlhip.RainbowLearner over a NoisyApproximator = fold both nets (counter = the learner's update count) -> draw -> gather ->
+ * rlhip_c51_grad_batch_f32 on the effective vectors -> [priority write-back] -> unfold -> rlhip_clip_adam_f32 on the noisy vector ->
+ * target sync on the noisy vectors.  Out of scope: independent (non-factorised) noise, per-sample noise inside a batch, noisy QR-DQN /
+ * IQN / scalar DQN, noisy dueling and three-layer nets, sharded runs, a fused vec-step, bf16 nets. */
+int64_t rlhip_noisy_nparams(int64_t ns, int64_t h, int64_t n_out);
+int64_t rlhip_noisy_plan_tile(void);
+int32_t rlhip_noisy_init_f32(float* params, int64_t ns, int64_t h, int64_t n_out, uint64_t seed, uint32_t net_id, float sigma0,
+                             rlhip_stream_t stream);
+int32_t rlhip_noisy_c51_forward_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
+                                    float v_max, const float* obs, int64_t n, uint64_t seed, uint32_t env_id_base, uint32_t step,
+                                    float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream);
+int32_t rlhip_noisy_c51_plan_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
+                                 float v_max, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step,
+                                 int32_t* actions, float* q_out, rlhip_stream_t stream);
+int32_t rlhip_noisy_fold_f32(const float* noisy, float* eff, const float* noisy2, float* eff2, int64_t ns, int64_t h, int64_t n_out,
+                             uint64_t seed, uint32_t counter, rlhip_stream_t stream);
+int32_t rlhip_noisy_unfold_grad_f32(const float* grad_eff, float* grad_noisy, int64_t ns, int64_t h, int64_t n_out, uint64_t seed,
+                                    uint32_t counter, rlhip_stream_t stream);
 
 #ifdef __cplusplus
 }

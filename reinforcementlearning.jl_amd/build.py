@@ -32,7 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 NO_SLP = ["-fno-slp-vectorize", "-fno-vectorize"]  # (the loop vectorizer packs 2-trip loops over the actions the same way)
 # (iqn.hip, the newest MFMA source, also switches the packed f32 instructions off at the target: no pass may form them)
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP, "iqn.hip": NO_SLP + NO_PK}
+EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP, "iqn.hip": NO_SLP + NO_PK,
+         "noisy.hip": NO_PK}  # (no MFMA in noisy.hip: the vectorizers stay on, the packed f32 forms are off at the target)
 
 
 def sources():

@@ -17,14 +17,11 @@
 //                          tile through the workgroup's own partial row
 //   c51_reduce_kernel      the partial rows, one per workgroup, ascending
 // No float atomics anywhere: two calls on the same inputs give the same bytes.
-#include "dist_device.h"  // c51_layer1, c51_logits: the two forward chains, shared with qrdqn.hip
+#include "dist_device.h"  // c51_layer1, c51_logits: the two forward chains, shared with qrdqn.hip; c51_atom, c51_probs_q: with noisy.hip
 #include "select_device.h"
 
 namespace rlhip {
 
-constexpr int C51_MAXA = 64;         // atoms
-constexpr int C51_MAXM = 256;        // output rows = na * n_atoms
-constexpr int C51_HMAX = 256;
 constexpr int C51_PT = 16;           // plan: envs per workgroup
 constexpr int C51_PTHREADS = 256;
 constexpr int C51_GT = 8;            // gradient: samples per tile
@@ -36,64 +33,6 @@ constexpr int64_t C51_MAX_PARTIAL_BYTES = 16 << 20;  // ... and at most 16 MiB o
 constexpr int C51_AS = C51_MAXA + 1; // per-sample atom rows in LDS are 65 floats apart
 constexpr int C51_GPOW = 33;         // gamma^n for n = 0..32
 constexpr int C51_WCH = 16;          // weights of a W2 row requested together (the logits pass, dh)
-
-__device__ __forceinline__ float c51_atom(int k, float v_min, float delta) { return fmaf((float)k, delta, v_min); }
-
-// The per-atom loops below run in chunks of C51_ACH atoms: the chunk is read from LDS first, its expf / divisions are independent of
-// each other (one thread owns a whole distribution: instruction-level parallelism is all it has), and the sums are then taken atom by
-// atom in ascending k, so the chunking changes no rounding.  An atom beyond n_atoms is read from a clamped index and dropped by a select.
-// The gradient kernel uses chunks of 8; the plan kernel, whose workgroups each pass once through their code, keeps the plain loops
-// (chunks of 1: with the unrolled bodies it measured 23.4 us at 4096 envs, with the loops 17.8 -- profiles/c51.md).
-constexpr int C51_ACH = 8;
-
-// e[k] = expf(l[k] - mx), S = sum_k e[k] in ascending k -> S (e may alias l)
-template <int ACH>
-__device__ __forceinline__ float c51_exp_sum(const float* l, float* e, int n_atoms, float& mx) {
-    mx = l[0];
-    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
-        float v[ACH];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : 0];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) mx = v[u] > mx ? v[u] : mx;
-    }
-    float S = 0.f;
-    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
-        float v[ACH];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : n_atoms - 1];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) v[u] = expf(v[u] - mx);
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) {
-            if (k0 + u < n_atoms) e[k0 + u] = v[u];
-            S = (k0 + u < n_atoms) ? S + v[u] : S;
-        }
-    }
-    return S;
-}
-
-// logits of one action -> its probabilities (in place) and Q = sum_k z_k p_k, both in ascending k
-template <int ACH>
-__device__ __forceinline__ float c51_probs_q(float* l, int n_atoms, float v_min, float delta) {
-    float mx;
-    const float S = c51_exp_sum<ACH>(l, l, n_atoms, mx);
-    float q = 0.f;
-    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
-        float v[ACH];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : n_atoms - 1];
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) v[u] = v[u] / S;
-#pragma unroll
-        for (int u = 0; u < ACH; ++u) {
-            if (k0 + u < n_atoms) l[k0 + u] = v[u];
-            const float t = fmaf(c51_atom(k0 + u, v_min, delta), v[u], q);
-            q = (k0 + u < n_atoms) ? t : q;
-        }
-    }
-    return q;
-}
 
 struct C51PlanArgs {
     const float* params;

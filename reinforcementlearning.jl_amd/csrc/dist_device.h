@@ -1,6 +1,7 @@
 // dist_device.h -- the two forward chains the distributional learners share (csrc/c51.hip, csrc/qrdqn.hip): layer 1 of a tile into LDS
 // and the output rows of mlp2(ns, h, M = na * N), "thread = output row".  include/rlhip.h (the C51 section) states both chains; the
-// functions keep the names they had in c51.hip, from which they were moved unchanged.
+// functions keep the names they had in c51.hip, from which they were moved unchanged.  Below them: logits -> probabilities -> Q
+// (c51_probs_q), which noisy.hip shares with c51.hip.
 #pragma once
 #include "mlp_device.h"
 
@@ -68,6 +69,69 @@ __device__ __forceinline__ void c51_logits(const float* __restrict__ P, int ns, 
     }
 #pragma unroll
     for (int s = 0; s < SPT; ++s) l_l[(i0 + s) * ls + m] = acc[s];
+}
+
+// ---- logits -> probabilities -> Q, shared by c51.hip and noisy.hip (moved unchanged from c51.hip)
+constexpr int C51_MAXA = 64;         // atoms
+constexpr int C51_MAXM = 256;        // output rows = na * n_atoms
+constexpr int C51_HMAX = 256;
+
+__device__ __forceinline__ float c51_atom(int k, float v_min, float delta) { return fmaf((float)k, delta, v_min); }
+
+// The per-atom loops below run in chunks of C51_ACH atoms: the chunk is read from LDS first, its expf / divisions are independent of
+// each other (one thread owns a whole distribution: instruction-level parallelism is all it has), and the sums are then taken atom by
+// atom in ascending k, so the chunking changes no rounding.  An atom beyond n_atoms is read from a clamped index and dropped by a select.
+// The gradient kernel uses chunks of 8; the plan kernel, whose workgroups each pass once through their code, keeps the plain loops
+// (chunks of 1: with the unrolled bodies it measured 23.4 us at 4096 envs, with the loops 17.8 -- profiles/c51.md).
+constexpr int C51_ACH = 8;
+
+// e[k] = expf(l[k] - mx), S = sum_k e[k] in ascending k -> S (e may alias l)
+template <int ACH>
+__device__ __forceinline__ float c51_exp_sum(const float* l, float* e, int n_atoms, float& mx) {
+    mx = l[0];
+    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
+        float v[ACH];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : 0];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) mx = v[u] > mx ? v[u] : mx;
+    }
+    float S = 0.f;
+    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
+        float v[ACH];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : n_atoms - 1];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) v[u] = expf(v[u] - mx);
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) {
+            if (k0 + u < n_atoms) e[k0 + u] = v[u];
+            S = (k0 + u < n_atoms) ? S + v[u] : S;
+        }
+    }
+    return S;
+}
+
+// logits of one action -> its probabilities (in place) and Q = sum_k z_k p_k, both in ascending k
+template <int ACH>
+__device__ __forceinline__ float c51_probs_q(float* l, int n_atoms, float v_min, float delta) {
+    float mx;
+    const float S = c51_exp_sum<ACH>(l, l, n_atoms, mx);
+    float q = 0.f;
+    for (int k0 = 0; k0 < n_atoms; k0 += ACH) {
+        float v[ACH];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) v[u] = l[k0 + u < n_atoms ? k0 + u : n_atoms - 1];
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) v[u] = v[u] / S;
+#pragma unroll
+        for (int u = 0; u < ACH; ++u) {
+            if (k0 + u < n_atoms) l[k0 + u] = v[u];
+            const float t = fmaf(c51_atom(k0 + u, v_min, delta), v[u], q);
+            q = (k0 + u < n_atoms) ? t : q;
+        }
+    }
+    return q;
 }
 
 }  // namespace rlhip

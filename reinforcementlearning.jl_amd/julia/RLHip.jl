@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner, HipNoisyApproximator
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2372,6 +2372,81 @@ function optimise!(L::HipIQNLearner, s, a, r, term, s_next; batch = L.batchsize,
     L.n_updates += 1
     optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
     true
+end
+
+# ------------------------------------------------------------------------------------------------------------ NoisyDense networks
+# The ccalls of csrc/noisy.hip (include/rlhip.h, "NoisyDense networks for the categorical learner"): factorised Gaussian noise, the noisy
+# vector [μ | σ] with each half in the plain two-layer layout.  Acting reads the noisy vector and draws per env inside the launch
+# (noisy_forward!, noisy_plan!); learning folds one sample per update into `params` (resample!), runs the C51 gradient entry on it
+# unchanged and maps the gradient back (optimise!).  Statically checked only: nothing in this module has been executed.
+
+"FluxApproximator(model = Chain(NoisyDense(ns, h, act), NoisyDense(h, n_out)), optimiser = Adam(lr)); `params` is the effective plain
+vector of the latest fold, `m` / `v` / `grad` have the noisy vector's length"
+mutable struct HipNoisyApproximator <: AbstractLearner
+    n_in::Int; hidden::Int; n_out::Int; act::Int32
+    noisy::DevBuf{Float32}; params::DevBuf{Float32}; grad::DevBuf{Float32}
+    m::DevBuf{Float32}; v::DevBuf{Float32}; beta_pow::DevBuf{Float32}; gn::DevBuf{Float32}
+    lr::Float32; beta1::Float32; beta2::Float32; eps::Float32
+    seed::UInt64; counter::UInt32
+end
+function HipNoisyApproximator(n_in, hidden, n_out; act = 0, lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, seed = 0, net_id = 0,
+                              sigma0 = 0.5f0)
+    nn = ccall((:rlhip_noisy_nparams, LIB), Int64, (Int64, Int64, Int64), n_in, hidden, n_out)
+    nn > 0 || throw(ArgumentError("HipNoisyApproximator: obs_dim 2..16, hidden a multiple of 4 and <= 256, 2..256 output rows"))
+    p = DevBuf{Float32}(nn)
+    chk(ccall((:rlhip_noisy_init_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int64, UInt64, UInt32, Float32, Ptr{Cvoid}),
+              p.ptr, n_in, hidden, n_out, seed, net_id, sigma0, stream()))
+    A = HipNoisyApproximator(n_in, hidden, n_out, act, p, DevBuf{Float32}(nn ÷ 2), DevBuf{Float32}(nn), DevBuf{Float32}(nn),
+                             DevBuf{Float32}(nn), to_dev!(DevBuf{Float32}(2), Float32[beta1, beta2]), DevBuf{Float32}(1), lr, beta1, beta2,
+                             eps, seed, 0)
+    resample!(A, 0)
+    A
+end
+
+"params <- μ + σ .* ξ under (seed, counter); `target_noisy` / `target`: the target net's pair, folded in the same launch under its own tag"
+function resample!(A::HipNoisyApproximator, counter; target_noisy = nothing, target = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    A.counter = counter
+    chk(ccall((:rlhip_noisy_fold_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              A.noisy.ptr, A.params.ptr, np(target_noisy), np(target), A.n_in, A.hidden, A.n_out, A.seed, A.counter, stream()))
+    A
+end
+
+"`grad`: the gradient of `params` as the plain kernels wrote it -> [dμ | dσ] with the draws of the latest fold, then clip + Adam on the
+noisy vector"
+function optimise!(A::HipNoisyApproximator, grad::DevBuf{Float32}; clip_norm = 0f0, grad_scale = 1f0)
+    chk(ccall((:rlhip_noisy_unfold_grad_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              grad.ptr, A.grad.ptr, A.n_in, A.hidden, A.n_out, A.seed, A.counter, stream()))
+    chk(ccall((:rlhip_clip_adam_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Float32,
+               Float32, Ptr{Cvoid}, Ptr{Cvoid}),
+              A.noisy.ptr, A.grad.ptr, A.m.ptr, A.v.ptr, A.beta_pow.ptr, A.noisy.n, grad_scale, clip_norm, A.lr, A.beta1,
+              A.beta2, A.eps, A.gn.ptr, stream()))
+    A
+end
+
+"forward of the categorical learner with an independent noise sample per env: `q` (n_actions, n); `probs` / `logits` may be `nothing`"
+function noisy_forward!(q::DevBuf{Float32}, A::HipNoisyApproximator, n_actions, n_atoms, v_min, v_max, obs::DevBuf{Float32}, n;
+                        seed = A.seed, env_id_base = UInt32(0), step = UInt32(0), probs = nothing, logits = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_noisy_c51_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              A.noisy.ptr, A.n_in, A.hidden, n_actions, n_atoms, A.act, v_min, v_max, obs.ptr, n, seed, env_id_base, step, q.ptr,
+              np(probs), np(logits), stream()))
+    q
+end
+
+"plan! in one launch: byte for byte noisy_forward! followed by the EpsilonGreedyExplorer's selection (no tie-break); ϵ is normally 0"
+function noisy_plan!(actions::DevBuf{Int32}, A::HipNoisyApproximator, n_actions, n_atoms, v_min, v_max, obs::DevBuf{Float32}, n, ϵ;
+                     seed = UInt64(0), env_id_base = UInt32(0), step = UInt32(0), q = nothing)
+    chk(ccall((:rlhip_noisy_c51_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              A.noisy.ptr, A.n_in, A.hidden, n_actions, n_atoms, A.act, v_min, v_max, obs.ptr, n, ϵ, seed, env_id_base, step,
+              actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
+    actions
 end
 
 end # module

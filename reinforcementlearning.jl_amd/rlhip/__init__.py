@@ -22,6 +22,7 @@ from .sac import SACPolicy  # noqa: F401
 from .c51 import RainbowLearner, c51_forward, c51_grad_batch, c51_plan, c51_workspace  # noqa: F401
 from .qrdqn import QRDQNLearner, qrdqn_forward, qrdqn_grad_batch, qrdqn_plan, qrdqn_workspace  # noqa: F401
 from .iqn import IQNApproximator, IQNLearner, iqn_forward, iqn_grad_batch, iqn_nparams, iqn_plan, iqn_workspace  # noqa: F401
+from .noisy import NoisyApproximator, noisy_c51_forward, noisy_c51_plan, noisy_init, noisy_nparams, noisy_plan_tile  # noqa: F401
 from .trajectory import (BatchSampler, CircularArraySARTSTraces, CircularPrioritizedFrameTraces, CircularPrioritizedTraces,  # noqa: F401
                          DoubleTargetFold, NStepBatchSampler, InsertSampleRatioController, Trajectory)
 

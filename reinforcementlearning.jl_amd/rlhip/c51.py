@@ -6,14 +6,18 @@ distribution".  The Zoo's RainbowLearner left the tree with the rest of the Zoo,
 implements it, tests/c51_ref.py replays it).  The network is the shipped two-layer layout with n_actions * n_atoms output rows,
 row k + n_atoms * o = atom k of action o.
 
-Out of scope, refused by name: NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
-heads, sharded runs (world > 1), UInt8 frames.
+NoisyDense networks: RainbowLearner over TargetNetwork(NoisyApproximator(...)) (rlhip/noisy.py) -- plan!, forward and distribution draw
+an independent noise sample per env from the noisy vector; every update folds fresh online and target noise first.
+
+Out of scope, refused by name: a fused vec-step, three-layer and bf16 networks, dueling distributional heads, sharded runs
+(world > 1), UInt8 frames.
 """
 import torch
 
 from . import _lib
 from ._lib import call
-from .dqn import DQNLearner, _Scratch
+from .dqn import DQNLearner, _Scratch, refuse_noisy
+from .noisy import noisy_c51_forward, noisy_c51_plan
 from .ops import ptr, stream_ptr
 
 ENVELOPE = "obs_dim 2..16, hidden a multiple of 4 and <= 256, 1..4 actions, n_atoms 2..64"
@@ -78,11 +82,15 @@ class DistributionalLearner(DQNLearner):
     on record rings (ns 2..4) and frame rings (ns 5..16).  The gate, the counters and the tail are DQNLearner's (`should_update_`,
     `_draw_`, `_is_weights_`, `_exchange_and_apply_`).  Messages name the learner's own type."""
 
-    def _check_approximator_(self, approximator, process_group, n_actions, n_rows, rows, net_doc):
+    def _check_approximator_(self, approximator, process_group, n_actions, n_rows, rows, net_doc, allow_noisy=False):
         name = type(self).__name__
         net = getattr(approximator, "network", None)
         if net is None or not hasattr(approximator, "target"):
             raise TypeError(f"{name}: the approximator is a TargetNetwork(HipApproximator(ns, h, {net_doc}))")
+        if not allow_noisy:
+            refuse_noisy(net, name)
+        elif getattr(net, "noisy_params", None) is not None and process_group is not None:
+            raise NotImplementedError(f"{name}: a NoisyApproximator with a process group (a sharded run) is out of scope")
         if getattr(net, "dueling_params", None) is not None:
             raise NotImplementedError(f"{name}: a DuelingApproximator (dueling distributional heads) is out of scope; use a "
                                       "HipApproximator")
@@ -167,7 +175,7 @@ class RainbowLearner(DistributionalLearner):
                  update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
                  double_dqn=False):
         n_actions, n_atoms = int(n_actions), int(n_atoms)
-        net = self._check_approximator_(approximator, process_group, n_actions, n_atoms, "n_atoms", "n_actions * n_atoms")
+        net = self._check_approximator_(approximator, process_group, n_actions, n_atoms, "n_atoms", "n_actions * n_atoms", allow_noisy=True)
         if not float(v_min) < float(v_max) or not all(map(lambda v: abs(float(v)) < float("inf"), (v_min, v_max))):
             raise ValueError(f"RainbowLearner: the support needs finite v_min < v_max, got [{v_min}, {v_max}]")
         if int(update_freq) < 1 or int(batchsize) < 1:
@@ -177,6 +185,7 @@ class RainbowLearner(DistributionalLearner):
         self.n_actions, self.n_atoms, self.v_min, self.v_max = n_actions, n_atoms, float(v_min), float(v_max)
         self._init_update_state_(approximator, batchsize, gamma, min_replay_history, update_freq, max_grad_norm, seed, process_group,
                                  per_eps, per_alpha, per_beta, n_step, double_dqn)
+        self.forward_ctr = 0  # the noise key of forward / distribution outside plan! (a NoisyApproximator)
         # the per-sample cross-entropy, then its priority
         self.ce = torch.zeros(self.batchsize, dtype=torch.float32, device=net.params.device)
 
@@ -185,20 +194,44 @@ class RainbowLearner(DistributionalLearner):
         net = self.approximator.network
         return net.params, net.n_in, net.hidden, self.n_actions, self.n_atoms, net.act, self.v_min, self.v_max
 
-    def forward(self, x):
-        """forward(learner, s) -> Q (na, n), the expectation of every action's distribution"""
+    def _noisy_args(self):
+        """a NoisyApproximator is evaluated from its noisy vector, never from `.params` (one stale sample of the last update)"""
+        return (self.approximator.network.noisy_params,) + self._net_args()[1:]
+
+    @property
+    def _noisy(self):
+        return getattr(self.approximator.network, "noisy_params", None) is not None
+
+    def _forward_key(self, seed, step):
+        """(seed, step) of a noisy forward outside plan!: without them every call draws new noise"""
+        if step is None:
+            step, self.forward_ctr = self.forward_ctr, self.forward_ctr + 1
+        return (self.seed if seed is None else seed), step
+
+    def forward(self, x, seed=None, env_id_base=0, step=None):
+        """forward(learner, s) -> Q (na, n), the expectation of every action's distribution; (seed, env_id_base, step): the key of a
+        NoisyApproximator's per-env noise"""
+        if self._noisy:
+            seed, step = self._forward_key(seed, step)
+            return noisy_c51_forward(*self._noisy_args(), x, seed, env_id_base, step)
         return c51_forward(*self._net_args(), x)
 
-    def distribution(self, x):
+    def distribution(self, x, seed=None, env_id_base=0, step=None):
         """-> (Q (na, n), probabilities (n_atoms, na, n))"""
         probs = torch.empty((self.n_actions * self.n_atoms, x.shape[1]), dtype=torch.float32, device=x.device)
-        q = c51_forward(*self._net_args(), x, probs=probs)
+        if self._noisy:
+            seed, step = self._forward_key(seed, step)
+            q = noisy_c51_forward(*self._noisy_args(), x, seed, env_id_base, step, probs=probs)
+        else:
+            q = c51_forward(*self._net_args(), x, probs=probs)
         return q, probs.view(self.n_actions, self.n_atoms, -1).permute(1, 0, 2)
 
     def plan_distributional_(self, obs, eps, seed, env_id_base, step, actions=None, q_out=None):
         """QBasedPolicy's plan! for this learner: the expectation of the distribution and the eps-greedy choice in one launch"""
         if q_out is not None and q_out.shape[0] != self.n_actions:
             q_out = None
+        if self._noisy:
+            return noisy_c51_plan(*self._noisy_args(), obs, eps, seed, env_id_base, step, actions, q_out)
         return c51_plan(*self._net_args(), obs, eps, seed, env_id_base, step, actions, q_out)
 
     # -------------------------------------------------------------------------------- optimise!
@@ -206,6 +239,8 @@ class RainbowLearner(DistributionalLearner):
         s, a, r, t, sn, n_used = batch
         tn = self.approximator
         net = tn.network
+        if self._noisy:  # fresh, independent noise for the online and the target net of this update: `.params` and `target` are rewritten
+            net.resample_(self.n_updates, tn)
         ws = self.workspace if a.numel() == self.batchsize else None
         c51_grad_batch(net.n_in, net.hidden, self.n_actions, self.n_atoms, net.act, self.v_min, self.v_max, net.params, tn.target, s, a, r,
                        t, sn, gamma, n_used, weights, self.double_dqn, ws, self.grad, self.loss, self.ce)

@@ -370,6 +370,11 @@ def _refuse_sac(policy, loop):
     """the fused vec-steps are DQN's: a SACPolicy runs on the per-stage loop"""
     if type(policy).__name__ == "SACPolicy":
         raise NotImplementedError(f"{loop}: a fused vec-step for SACPolicy is out of scope; use the per-stage loop, rlhip.run")
+    net = getattr(getattr(getattr(policy, "learner", None), "approximator", None), "network", None)
+    if getattr(net, "noisy_params", None) is not None:
+        # (the vec-step kernels act on `.params`: with a NoisyApproximator that is one stale noise sample, shared by every env)
+        raise NotImplementedError(f"{loop}: a fused vec-step for a NoisyApproximator (NoisyDense networks, per-env noise) is out of scope; "
+                                  "use the per-stage loop, rlhip.run")
     if hasattr(getattr(policy, "learner", None), "plan_distributional_"):
         # (the vec-step kernels plan on scalar Q-values and train on Huber(TD))
         if type(policy.learner).__name__ == "IQNLearner":

@@ -68,6 +68,13 @@ def check_wide_net(net, who):
                                   "use a two-layer HipApproximator / DuelingApproximator (layers = 2)")
 
 
+def refuse_noisy(net, who):
+    """the refusal of every learner and loop that reads `.params` to act: with a NoisyApproximator that is one stale noise sample"""
+    if getattr(net, "noisy_params", None) is not None:
+        raise NotImplementedError(f"{who}: a NoisyApproximator (NoisyDense networks) trains under RainbowLearner on the per-stage loop, "
+                                  "rlhip.run; noisy QR-DQN / IQN / scalar DQN and a fused vec-step are out of scope")
+
+
 def dqn_plan_obsn(params, ns, h, na, act, obs, eps, seed, env_id_base, step, actions=None, q_out=None):
     """`dqn_plan` for observations of 5..16 components (rlhip_dqn_plan_obsn_f32): byte for byte `mlp2_forward` then `eps_greedy_select`"""
     n = obs.shape[1]
@@ -330,7 +337,8 @@ class DuelingApproximator(HipApproximator):
 
 class TargetNetwork:
     """TargetNetwork(network; sync_freq = 1, ρ = 0f0)  target_network.jl:27-60.  With a DuelingApproximator the target is kept as a
-    dueling vector too (`target_dueling`): Polyak runs on the dueling vectors and `target`, the effective vector, is folded again."""
+    dueling vector too (`target_dueling`): Polyak runs on the dueling vectors and `target`, the effective vector, is folded again.
+    With a NoisyApproximator likewise (`target_noisy`); `target` is then written by the learner's next `resample_`, under fresh noise."""
 
     def __init__(self, network, sync_freq=1, rho=0.0):
         if not 0 <= rho <= 1:
@@ -340,6 +348,8 @@ class TargetNetwork:
         self.target_packed = network.packed.clone() if getattr(network, "layers", 2) == 3 else None
         if getattr(network, "dueling_params", None) is not None:
             self.target_dueling = network.dueling_params.clone()
+        if getattr(network, "noisy_params", None) is not None:
+            self.target_noisy = network.noisy_params.clone()
 
     def forward(self, x):
         return self.network.forward(x)
@@ -356,6 +366,8 @@ class TargetNetwork:
             if getattr(net, "dueling_params", None) is not None:
                 polyak_(self.target_dueling, net.dueling_params, self.rho)
                 fold_dueling(self.target_dueling, self.target, net.n_in, net.hidden, net.n_out, getattr(net, "layers", 2))
+            elif getattr(net, "noisy_params", None) is not None:
+                polyak_(self.target_noisy, net.noisy_params, self.rho)
             else:
                 polyak_(self.target, self.network.params, self.rho)
             self.n_optimise = 0
@@ -405,6 +417,7 @@ class DQNLearner:
         self.per_eps, self.per_alpha, self.per_beta = float(per_eps), float(per_alpha), per_beta
         self.approximator = approximator  # a TargetNetwork
         net = approximator.network
+        refuse_noisy(net, "DQNLearner")
         self.batchsize, self.gamma, self.delta = batchsize, gamma, huber_delta
         self.min_replay_history, self.update_freq, self.max_grad_norm = min_replay_history, update_freq, max_grad_norm
         if int(update_freq) < 1:
@@ -637,6 +650,8 @@ class QBasedPolicy:
         if wide:
             check_wide_net(net, "QBasedPolicy")
         dist = getattr(self.learner, "plan_distributional_", None)  # a learner whose network estimates a value DISTRIBUTION per action
+        if dist is None:
+            refuse_noisy(net, "QBasedPolicy")
         if ex.is_break_tie:  # tie-break variant: unfused path (forward, then the selection kernel)
             values = self.learner.forward(env.state()) if dist is not None else net.forward(env.state())
             return ex.plan_(values, env_id_base=env.env_id_base)

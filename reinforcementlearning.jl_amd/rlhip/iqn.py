@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import call
 from .c51 import DistributionalLearner, _opt
-from .dqn import HipApproximator
+from .dqn import HipApproximator, refuse_noisy
 from .ops import ptr, stream_ptr
 
 ENVELOPE = "obs_dim 2..16, hidden a multiple of 32 and <= 256, 1..4 actions, n_cos even and 2..64, 1..64 levels"
@@ -112,6 +112,7 @@ class IQNLearner(DistributionalLearner):
                  update_freq=1, max_grad_norm=0.0, seed=0, process_group=None, per_eps=1e-6, per_alpha=0.6, per_beta=0.0, n_step=1,
                  double_dqn=False):
         n_actions, N, N_target, K = int(n_actions), int(N), int(N_target), int(K)
+        refuse_noisy(getattr(approximator, "network", None), "IQNLearner")
         if getattr(getattr(approximator, "network", None), "n_cos", None) is None:
             raise TypeError("IQNLearner: the approximator is a TargetNetwork(IQNApproximator(ns, h, n_actions, n_cos)); NoisyDense, "
                             "three-layer and bf16 networks are out of scope")

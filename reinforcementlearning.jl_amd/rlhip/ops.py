@@ -427,6 +427,19 @@ def td_target(qt_next, reward, terminal, gamma):
 
 
 # ----------------------------------------------------------------------------------------- misc
+def noisy_fold(noisy, eff, n_in, h, n_out, seed, counter, noisy2=None, eff2=None):
+    """noisy vector(s) [mu | sigma] -> effective plain vector(s) mu + sigma .* xi under (seed, counter), one launch (csrc/noisy.hip);
+    the second pair is the target net, drawn under a Philox tag of its own"""
+    call("rlhip_noisy_fold_f32", ptr(noisy), ptr(eff), ptr(noisy2), ptr(eff2), n_in, h, n_out, seed, counter, stream_ptr())
+    return eff
+
+
+def noisy_unfold_grad(grad_eff, grad_noisy, n_in, h, n_out, seed, counter):
+    """gradient of the effective vector -> gradient of the noisy vector [g | g .* xi], the online draws of (seed, counter) regenerated"""
+    call("rlhip_noisy_unfold_grad_f32", ptr(grad_eff), ptr(grad_noisy), n_in, h, n_out, seed, counter, stream_ptr())
+    return grad_noisy
+
+
 def fill_uniform(n, seed, t, tag, device="cuda"):
     out = torch.empty(n, dtype=torch.float32, device=device)
     call("rlhip_fill_uniform_f32", ptr(out), n, seed, t, tag, stream_ptr())
