@@ -21,6 +21,7 @@
 //                 the stored h (h > 0 <=> z > 0), so both phases see one z
 //   dqn_batch_reduce_kernel          the partial rows, one per workgroup, in a fixed order (include/rlhip.h states it)
 // No float atomics anywhere: two calls on the same inputs give the same bytes.
+#include "dist_host.h"  // dist_check_actions
 #include "mlp_device.h"
 #include "select_device.h"
 
@@ -341,13 +342,6 @@ __global__ __launch_bounds__(256) void dqn_batch_reduce_kernel(const float* __re
     }
 }
 
-#ifdef RLHIP_BOUNDS_CHECK
-__global__ __launch_bounds__(256) void dqn_batch_count_bad_actions_kernel(const int32_t* __restrict__ a, int64_t batch, int na, int* __restrict__ n_bad) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch && (a[b] < 0 || a[b] >= na)) atomicAdd(n_bad, 1);
-}
-#endif
-
 struct RegQn {
     const float* q;
     __device__ __forceinline__ float operator()(int k) const { return q[k]; }
@@ -451,21 +445,10 @@ int32_t rlhip_dqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int32_t act,
     RLHIP_REQUIRE(batch >= 1, "empty batch");
     RLHIP_REQUIRE(params && target_params && s && a && r && term && s_next && workspace && grad_out && loss_out, "NULL argument");
     hipStream_t st = as_stream(stream);
-#ifdef RLHIP_BOUNDS_CHECK
-    {  // the debug build: an action outside 0 .. na - 1 is an error instead of a sample without a gradient
-        int* cnt = (int*)workspace;
-        int n_bad = 0;
-        RLHIP_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int), st));
-        hipLaunchKernelGGL(dqn_batch_count_bad_actions_kernel, dim3((int)((batch + 255) / 256)), dim3(256), 0, st, a, batch, (int)na, cnt);
-        RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK_HIP(hipMemcpyAsync(&n_bad, cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-        RLHIP_CHECK_HIP(hipStreamSynchronize(st));
-        if (n_bad) {
-            ::rlhip::set_error("%s:%d: %d of %lld actions are outside 0 .. %lld", __FILE__, __LINE__, n_bad, (long long)batch, (long long)na - 1);
-            return RLHIP_EINVAL;
-        }
+    {  // (dist.hip: the check the distributional learners make; nothing in the default build)
+        const int32_t rc = dist_check_actions(a, batch, na, workspace, st, __FILE__, __LINE__);
+        if (rc) return rc;
     }
-#endif
     const int64_t np = mlp2_nparams(ns, h, na);
     DqnBatchArgs g;
     g.params = params, g.tparams = target_params;

@@ -7,7 +7,7 @@
 // (rows x n_cos) x (n_cos x h) product in front of the head.  A workgroup of 256 threads walks the rows of a tile of 8 samples in
 // blocks of 32:
 //   staging      Wphi | bphi (a straight copy: column-major h x n_cos is the B-operand image) and W2 | b2 of the net in LDS, once per
-//                net and tile; psi of the tile's samples once per sample (c51_layer1), not once per level
+//                net and tile; psi of the tile's samples once per sample (dist_layer1), not once per level
 //   cos block    c[row][e] = cospif((e + 1) tau_row) for the block's 32 rows -> LDS, rows 65 floats apart (the A-operand image)
 //   phi block    v_mfma_f32_32x32x2_f32: 32 rows x 32 hidden units per instruction, n_cos / 2 k-steps, bphi as the accumulator's
 //                initial value, so that the chain is the header's ascending-e fmaf chain bit for bit (tools/micro/mfma_f32_l1.hip,
@@ -18,9 +18,10 @@
 //                (ascending), accumulators living in registers for the whole launch
 //   pairwise     one thread per (sample, n): theta_n of the action's head row, then the two chains over the targets T_j in LDS
 // Every gradient element is ONE chain from +0 over the workgroup's rows, kept in registers and stored once into the workgroup's
-// partial row; iqn_reduce_kernel adds the rows in ascending order.  No float atomics: two calls give the same bytes.
-#include "dist_device.h"
-#include "select_device.h"
+// partial row; dist_reduce_kernel (dist.hip) adds the rows in ascending order.  No float atomics: two calls give the same bytes.
+// The tile loads, the gamma table, the per-tile scalars, psi's chain and a* are the stages of dist_device.h, shared with c51.hip and
+// qrdqn.hip; the register chains above are this file's own.
+#include "dist_host.h"
 
 namespace rlhip {
 
@@ -36,10 +37,7 @@ constexpr int IQ_HMAX = 256;
 constexpr int IQ_CS = IQ_MAXC + 1;          // cosine rows are 65 floats apart
 constexpr int IQ_AS = IQ_MAXL + 1;          // per-sample level rows are 65 floats apart
 constexpr int IQ_LS = MAXO * IQ_MAXL + 1;   // per-sample quantile rows (na * levels) are 257 floats apart
-constexpr int IQ_GPOW = 33;                 // gamma^n for n = 0..32
 constexpr int IQ_W1U = (IQ_HMAX * 16 + IQ_HMAX + IQ_NT - 1) / IQ_NT;  // dW1 | db1 elements per thread (17)
-constexpr int IQ_MAX_BLOCKS = 256;
-constexpr int64_t IQ_MAX_PARTIAL_BYTES = 16 << 20;
 
 __host__ __device__ __forceinline__ int64_t iqn_nparams(int64_t ns, int64_t h, int64_t na, int64_t nc) {
     return h * ns + h + h * nc + h + na * h + na;
@@ -183,10 +181,7 @@ __global__ __launch_bounds__(IQ_NT) void iqn_plan_kernel(IqnPlanArgs g) {
     const IqnLds L = iqn_lds(iq_dyn, h, nc);
     const int64_t e0 = (int64_t)blockIdx.x * T;
     const int nv = (int)(g.n - e0 < T ? g.n - e0 : T);
-    if (tid < 16 * T) {
-        const int i = tid % T, k = tid / T;
-        l_x[tid] = (k < ns && i < nv) ? g.obs[(int64_t)k * g.n + e0 + i] : 0.f;
-    }
+    dist_load_obs<T>(g.obs, g.n, e0, nv, ns, l_x);
     for (int q = tid; q < T * K; q += IQ_NT) {
         const int i = q / K, n = q - i * K;
         float tau = 0.f;
@@ -198,7 +193,7 @@ __global__ __launch_bounds__(IQ_NT) void iqn_plan_kernel(IqnPlanArgs g) {
     }
     iqn_stage(g.params, ns, h, na, nc, L);
     __syncthreads();
-    c51_layer1<ACT, T, IQ_NT>(g.params, ns, h, l_x, L.psi);
+    dist_layer1<ACT, T, IQ_NT>(g.params, ns, h, l_x, L.psi);
     iqn_rows_all(L, l_tau, K, nv * K, h, na, nc, l_c, l_th);
     if (g.quantiles_out) {
         for (int q = tid; q < na * K * T; q += IQ_NT) {
@@ -244,7 +239,7 @@ struct IqnGradArgs {
     uint64_t seed;
     uint32_t draw_ctr;
     float gamma, kappa, fNp, fNB;  // fNB = (float)N' * (float)batch, one Float32 product
-    float gpow[IQ_GPOW];
+    float gpow[DIST_GPOW];
 };
 
 // dWphi of the block: D[j][e] += dphi[row][j] * c[row][e] over the block's rows ascending (A[m = j][k = row], B[k = row][n = e])
@@ -274,7 +269,7 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
     __shared__ float l_T[T * AS], l_rho[T * AS];       // T_j, rho_n
     __shared__ float l_grow[IQ_RB];                    // g of the block's rows
     __shared__ float l_qt[MAXO * T], l_qo[MAXO * T];
-    __shared__ float l_r[T], l_cc[T], l_w[T], l_loss[T], l_gp[IQ_GPOW];
+    __shared__ float l_r[T], l_cc[T], l_w[T], l_loss[T], l_gp[DIST_GPOW];
     __shared__ int l_ai[T], l_as[T];
     const int ns = g.ns, h = g.h, na = g.na, nc = g.nc, N = g.N, Np = g.Np;
     const IqnLds L = iqn_lds(iq_dyn, h, nc);
@@ -288,20 +283,12 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
     float a_w1[IQ_W1U], a_w2[MAXO] = {0.f, 0.f, 0.f, 0.f}, a_b2 = 0.f, a_bphi = 0.f, s_loss = 0.f;
 #pragma unroll
     for (int u = 0; u < IQ_W1U; ++u) a_w1[u] = 0.f;
-    if (tid < IQ_GPOW) {  // the table is read from the kernel-argument segment with a per-lane index
-        const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-        l_gp[tid] = reinterpret_cast<const float*>(ka + offsetof(IqnGradArgs, gpow))[tid];
-    }
+    dist_load_gpow<IqnGradArgs>(l_gp);
 
     for (int tile = blockIdx.x; tile < g.num_tiles; tile += gridDim.x) {
         const int64_t b0 = (int64_t)tile * T;
         const int nv = (int)(g.batch - b0 < T ? g.batch - b0 : T);
-        if (tid < 16 * T) {
-            const int i = tid % T, k = tid / T;
-            const bool in = k < ns && i < nv;
-            l_x[tid] = in ? g.s[(int64_t)k * g.batch + b0 + i] : 0.f;
-            l_xn[tid] = in ? g.sn[(int64_t)k * g.batch + b0 + i] : 0.f;
-        }
+        dist_load_states<T>(g.s, g.sn, g.batch, b0, nv, ns, l_x, l_xn);
         for (int q = tid; q < T * N; q += NT) {  // tau: (batch position, draw_ctr), the online tag
             const int i = q / N, n = q - i * N;
             float tau = 0.f;
@@ -322,33 +309,14 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
         }
         for (int q = tid; q < T * (h + 1); q += NT) L.dpsi[q] = 0.f;
         __syncthreads();  // (also: l_gp is written)
-        if (tid < T) {
-            float r = 0.f, cc = 0.f, w = 1.0f;
-            int a = -1;
-            if (tid < nv) {
-                const int64_t b = b0 + tid;
-                r = g.r[b];
-                a = g.a[b];
-                if (a < 0 || a >= na) a = -1;  // the action is only ever COMPARED: one outside 0 .. na - 1 selects nothing
-                const float cont = g.term[b] ? 0.f : 1.f;
-                float disc = g.gamma;
-                if (g.n_used) {
-                    int nu = g.n_used[b];
-                    nu = nu < 0 ? 0 : (nu > IQ_GPOW - 1 ? IQ_GPOW - 1 : nu);
-                    disc = l_gp[nu];
-                }
-                cc = disc * cont;
-                if (g.isw) w = g.isw[b];
-            }
-            l_r[tid] = r, l_cc[tid] = cc, l_w[tid] = w, l_ai[tid] = a;
-        }
+        dist_tile_scalars<T>(g, b0, nv, l_gp, l_r, l_cc, l_w, l_ai);
         // ---- target net on s' at tau' [, online net on s' at the same tau']
         iqn_stage(g.tparams, ns, h, na, nc, L);
-        c51_layer1<ACT, T, NT>(g.tparams, ns, h, l_xn, L.psi);
+        dist_layer1<ACT, T, NT>(g.tparams, ns, h, l_xn, L.psi);
         iqn_rows_all(L, l_taup, Np, nv * Np, h, na, nc, l_c, l_tht);
         if (g.double_dqn) {  // (uniform)
             iqn_stage(g.params, ns, h, na, nc, L);
-            c51_layer1<ACT, T, NT>(g.params, ns, h, l_xn, L.psi);
+            dist_layer1<ACT, T, NT>(g.params, ns, h, l_xn, L.psi);
             iqn_rows_all(L, l_taup, Np, nv * Np, h, na, nc, l_c, l_tho);
         }
         if (tid < na * T) {
@@ -359,15 +327,7 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
             l_qo[o * T + i] = i < nv ? iqn_mean(l_tho + i * LS + o * Np, Np) : 0.f;
         }
         __syncthreads();
-        if (tid < T) {  // a*: the first maximum wins (strict >)
-            const float* q = g.double_dqn ? l_qo : l_qt;
-            int as = 0;
-            float mq = q[tid];
-            for (int o = 1; o < na; ++o)
-                if (q[o * T + tid] > mq) mq = q[o * T + tid], as = o;
-            l_as[tid] = as;
-            if (g.sel_out && tid < nv) g.sel_out[b0 + tid] = as;
-        }
+        dist_select_action<T>(g.double_dqn ? l_qo : l_qt, na, l_as, g.sel_out, b0, nv);
         __syncthreads();
         for (int q = tid; q < Np * T; q += NT) {  // T_j = fmaf(c, th_t(s', tau'_j)[a*], r)
             const int i = q % T, j = q / T;
@@ -380,7 +340,7 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
         }
         // ---- online net on s at tau, block by block: forward, pairwise term, backward
         if (!g.double_dqn) iqn_stage(g.params, ns, h, na, nc, L);
-        c51_layer1<ACT, T, NT>(g.params, ns, h, l_x, L.psi);
+        dist_layer1<ACT, T, NT>(g.params, ns, h, l_x, L.psi);
         const int nrows = nv * N;
         for (int row0 = 0; row0 < nrows; row0 += IQ_RB) {
             iqn_cos_block(l_tau, N, row0, nrows, nc, l_c);
@@ -506,23 +466,6 @@ __global__ __launch_bounds__(IQ_NT) void iqn_grad_kernel(IqnGradArgs g) {
     if (tid == 0) g.loss_partials[blockIdx.x] = s_loss;
 }
 
-// gradient element p and the loss: the partial rows / losses of workgroups 0, 1, .. in ascending order, from +0
-__global__ __launch_bounds__(256) void iqn_reduce_kernel(const float* __restrict__ partials, const float* __restrict__ loss_partials, int nb,
-                                                         int np, float* __restrict__ grad, float* __restrict__ loss, float fb) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < np) {
-        float acc = 0.f;
-#pragma unroll 8
-        for (int b = 0; b < nb; ++b) acc += partials[(int64_t)b * np + p];
-        grad[p] = acc;
-    }
-    if (p == 0) {
-        float a = 0.f;
-        for (int b = 0; b < nb; ++b) a += loss_partials[b];
-        loss[0] = a / fb;
-    }
-}
-
 // Glorot-uniform per Dense layer, zero biases, by the rule of mlp2_init_kernel: tensor ids net_id * 4 + {0: W1, 1: Wphi, 2: W2}
 __global__ __launch_bounds__(256) void iqn_init_kernel(float* __restrict__ p, int ns, int h, int na, int nc, uint64_t seed, uint32_t net_id) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -542,16 +485,16 @@ __global__ __launch_bounds__(256) void iqn_init_kernel(float* __restrict__ p, in
     p[q] = val;
 }
 
-// workgroups = partial rows: the nb rule of the C51 section
-static int64_t iqn_num_blocks(int64_t np, int64_t batch) {
-    const int64_t tiles = (batch + IQ_T - 1) / IQ_T;
-    int64_t cap = IQ_MAX_PARTIAL_BYTES / (np * (int64_t)sizeof(float));
-    cap = cap < 1 ? 1 : (cap > IQ_MAX_BLOCKS ? IQ_MAX_BLOCKS : cap);
-    return tiles < cap ? tiles : cap;
-}
+// the bounds of the net and of a number of levels, each stated once (dist_host.h: a list of bounds hands each one to B)
+#define IQ_NET_BOUNDS(B)                                                                  \
+    B(ns >= 2 && ns <= 16, "obs dim must be 2..16");                                      \
+    B(h >= 32 && h <= IQ_HMAX && h % 32 == 0, "hidden must be a multiple of 32, <= 256"); \
+    B(na >= 1 && na <= MAXO, "na must be 1..4");                                          \
+    B(n_cos >= 2 && n_cos <= IQ_MAXC && n_cos % 2 == 0, "n_cos must be even, 2..64")
 
-static bool iqn_net_ok(int64_t ns, int64_t h, int64_t na, int64_t nc) {
-    return ns >= 2 && ns <= 16 && h >= 32 && h <= IQ_HMAX && h % 32 == 0 && na >= 1 && na <= MAXO && nc >= 2 && nc <= IQ_MAXC && nc % 2 == 0;
+static bool iqn_net_ok(int64_t ns, int64_t h, int64_t na, int64_t n_cos) {
+    IQ_NET_BOUNDS(DIST_BOUND_HOLDS);
+    return true;
 }
 static bool iqn_levels_ok(int64_t n) { return n >= 1 && n <= IQ_MAXL; }
 
@@ -564,12 +507,9 @@ static int32_t iqn_allow_lds(K kernel, size_t bytes, unsigned long long* done) {
 
 using namespace rlhip;
 
-#define IQ_REQUIRE_NET()                                                                                            \
-    RLHIP_REQUIRE(ns >= 2 && ns <= 16, "obs dim must be 2..16");                                                    \
-    RLHIP_REQUIRE(h >= 32 && h <= IQ_HMAX && h % 32 == 0, "hidden must be a multiple of 32, <= 256");               \
-    RLHIP_REQUIRE(na >= 1 && na <= MAXO, "na must be 1..4");                                                        \
-    RLHIP_REQUIRE(n_cos >= 2 && n_cos <= IQ_MAXC && n_cos % 2 == 0, "n_cos must be even, 2..64");                   \
-    RLHIP_REQUIRE(act == 0 || act == 1, "act must be 0 (relu) or 1 (tanh)")
+#define IQ_REQUIRE_NET()           \
+    IQ_NET_BOUNDS(RLHIP_REQUIRE);  \
+    DIST_REQUIRE_ACT()
 
 static int32_t iqn_plan_launch(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t K, int32_t act, const float* obs,
                                int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step, int32_t* actions, float* q_out,
@@ -651,7 +591,7 @@ int64_t rlhip_iqn_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t n_c
                                   int64_t batch) {
     if (!iqn_net_ok(ns, h, na, n_cos) || !iqn_levels_ok(n_levels) || !iqn_levels_ok(n_target_levels) || batch < 1) return -1;
     const int64_t np = iqn_nparams(ns, h, na, n_cos);
-    return iqn_num_blocks(np, batch) * (np + 1) * (int64_t)sizeof(float);  // partial rows | partial losses
+    return dist_num_blocks(np, batch, IQ_T) * (np + 1) * (int64_t)sizeof(float);  // partial rows | partial losses
 }
 
 int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_levels, int64_t n_target_levels, int32_t act,
@@ -678,18 +618,15 @@ int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_co
     g.double_dqn = double_dqn ? 1 : 0;
     g.seed = seed, g.draw_ctr = draw_ctr;
     g.gamma = gamma, g.kappa = kappa, g.fNp = (float)n_target_levels, g.fNB = g.fNp * (float)batch;
-    for (int n = 0; n < IQ_GPOW; ++n) g.gpow[n] = rlhip_gamma_pow(gamma, n);
-    const int nb = (int)iqn_num_blocks(np, batch);
+    for (int n = 0; n < DIST_GPOW; ++n) g.gpow[n] = rlhip_gamma_pow(gamma, n);
+    const int nb = (int)dist_num_blocks(np, batch, IQ_T);
     g.partials = (float*)workspace;
     g.loss_partials = g.partials + (int64_t)nb * np;
     // the instantiation set: ACT in {0, 1}
     const int32_t rc = act == 0 ? iqn_launch_grad<0>(g, nb, st) : iqn_launch_grad<1>(g, nb, st);
     if (rc) return rc;
     RLHIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(iqn_reduce_kernel, dim3((int)((np + 255) / 256)), dim3(256), 0, st, g.partials, g.loss_partials, nb, (int)np, grad_out,
-                       loss_out, (float)batch);
-    RLHIP_LAUNCH_CHECK();
-    return RLHIP_OK;
+    return dist_reduce_launch(g.partials, g.loss_partials, nb, np, grad_out, loss_out, (float)batch, st);
 }
 
 }  // extern "C"

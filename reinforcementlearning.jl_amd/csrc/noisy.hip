@@ -17,15 +17,14 @@
 //         logits    thread = output row m: the W2mu row and the W2sg row stream from L2 once per tile, two accumulators per env, the
 //                   hidden values read as float4 LDS broadcasts.  With M <= 128 rows the two halves of the workgroup take half of the
 //                   tile's envs each (otherwise waves 2 and 3 would idle through the longest chain of the kernel)
-//         then C51's own lines: c51_probs_q per (env, action), eps_greedy_select1 per env
+//         then dist_plan_tail (dist_device.h), as c51_plan_kernel: c51_probs_q per (env, action), eps_greedy_select1 per env
 //   noisy_fold_kernel / noisy_unfold_kernel   LEARNING, one sample per update and net (NoisyNet-DQN): eff = fmaf(sigma, xi, mu) is a
 //       plain mlp2 vector that rlhip_c51_grad_batch_f32 takes unchanged; the gradient maps back as dmu = g, dsigma = g xi, the draws
 //       REGENERATED from the key.  Every workgroup stages the ns + 2h + M factors in LDS once, then streams its elements; blockIdx.y
 //       selects the net (online / target: two Philox tags) as in the dueling fold.
 // No float atomics, no cross-lane sums: two calls on the same inputs give the same bytes.
-#include "dist_device.h"
+#include "dist_host.h"    // dist_device.h; the lists of bounds
 #include "head_device.h"  // normal_draw_pair
-#include "select_device.h"
 
 namespace rlhip {
 
@@ -51,16 +50,9 @@ __device__ __forceinline__ void noisy_factor_pair(uint64_t seed, uint32_t id, ui
 struct NoisyPlanArgs {
     const float* noisy;
     const float* obs;
-    float* q_out;       // nullable
-    float* probs_out;   // nullable
-    float* logits_out;  // nullable
-    int32_t* actions;   // nullable: forward
-    int64_t n;
+    DistPlanOut out;  // rows_raw: logits, rows_out: probabilities
     int ns, h, na, n_atoms;
     float v_min, delta;
-    double eps;
-    uint64_t seed;
-    uint32_t env_id_base, step;
 };
 
 // rows m of SPT envs starting at i0: lmu = b2mu[m], fmaf(W2mu[m, j], hid[j], .);  lsg = b2sg[m], fmaf(W2sg[m, j], v[j], .), both over j
@@ -75,7 +67,7 @@ __device__ __forceinline__ void noisy_logits(const float* __restrict__ Pm, const
     const float bm = Wm[M * h + m], bs = Ws[M * h + m];
 #pragma unroll
     for (int s = 0; s < SPT; ++s) am[s] = bm, as[s] = bs;
-    // both rows come from L2 in chunks of WCH weights, the next chunk requested before the current one is used (c51_logits' scheme);
+    // both rows come from L2 in chunks of WCH weights, the next chunk requested before the current one is used (dist_rows' scheme);
     // weights beyond h are read from a clamped index and never used
     float cm[WCH], cs[WCH], nm[WCH], nsg[WCH];
 #pragma unroll
@@ -122,25 +114,22 @@ __device__ __forceinline__ void noisy_logits(const float* __restrict__ Pm, const
 
 template <int ACT, int T>
 __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArgs g) {
-    constexpr int NT = NZ_THREADS, LS = C51_MAXM + 1;
+    constexpr int NT = NZ_THREADS, LS = DIST_MAXM + 1;
     static_assert(16 * T <= NT && MAXO * T <= NT && T % 8 == 0, "thread maps of the tile; half a tile is a multiple of 4 envs");
     // LDS: static, sized for h = 256 and 256 rows (26 KB at T = 8, 51 KB at T = 16), so that every address is an immediate
     __shared__ float l_x[16 * T], l_a[16 * T];                                     // [k][T]: the observation, f of the input factors
-    __shared__ __attribute__((aligned(16))) float l_h[C51_HMAX * T];               // [j][T]: hid
-    __shared__ __attribute__((aligned(16))) float l_v[C51_HMAX * T];               // [j][T]: c .* hid
+    __shared__ __attribute__((aligned(16))) float l_h[DIST_HMAX * T];               // [j][T]: hid
+    __shared__ __attribute__((aligned(16))) float l_v[DIST_HMAX * T];               // [j][T]: c .* hid
     __shared__ float l_l[T * LS];                                                  // [i][m]: d, then logits, then probabilities
     __shared__ float l_q[MAXO * T];
     const int tid = threadIdx.x;
     const int ns = g.ns, h = g.h, na = g.na, n_atoms = g.n_atoms, M = na * n_atoms;
     const int64_t e0 = (int64_t)blockIdx.x * T;
-    const int nv = (int)(g.n - e0 < T ? g.n - e0 : T);
-    const uint32_t id0 = g.env_id_base + (uint32_t)e0;  // (wraps: the env id is a 32-bit counter word)
+    const int nv = (int)(g.out.n - e0 < T ? g.out.n - e0 : T);
+    const uint32_t id0 = g.out.env_id_base + (uint32_t)e0;  // (wraps: the env id is a 32-bit counter word)
     const float* Pm = g.noisy;
     const float* Ps = g.noisy + mlp2_nparams(ns, h, M);
-    if (tid < 16 * T) {
-        const int i = tid % T, k = tid / T;
-        l_x[tid] = (k < ns && i < nv) ? g.obs[(int64_t)k * g.n + e0 + i] : 0.f;
-    }
+    dist_load_obs<T>(g.obs, g.out.n, e0, nv, ns, l_x);
     // ---- phase A: a -> l_a, d -> the logit slots (a slot of an env beyond nv is drawn too: it is never stored)
     {
         const int npa = (ns + 1) >> 1, npd = (M + 1) >> 1;
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
             const int i = q % T, p = q / T;
             const int m0 = 2 * (p - npa);
             float f0, f1;  // (one draw call for both regions: a wave that holds both kinds does not run it twice)
-            noisy_factor_pair(g.seed, id0 + (uint32_t)i, g.step, p < npa ? NZ_QA + 2 * p : NZ_QD + m0, TAG_NOISY_ACT, f0, f1);
+            noisy_factor_pair(g.out.seed, id0 + (uint32_t)i, g.out.step, p < npa ? NZ_QA + 2 * p : NZ_QD + m0, TAG_NOISY_ACT, f0, f1);
             if (p < npa) {
                 l_a[(2 * p) * T + i] = f0, l_a[(2 * p + 1) * T + i] = f1;  // (2 p + 1 <= 15)
             } else {
@@ -161,7 +150,7 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
     // ---- phase B: layer 1, thread = (env i, hidden units j0, j0 + 1)
     for (int q = tid; q < (h >> 1) * T; q += NT) {
         const int i = q % T, j0 = 2 * (q / T);
-        // branch-free as in c51_layer1: a weight beyond ns is read from a clamped index and its fmaf dropped by a select
+        // branch-free as in dist_layer1: a weight beyond ns is read from a clamped index and its fmaf dropped by a select
         float wm0[16], wm1[16], ws0[16], ws1[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -171,8 +160,8 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
         float zm0 = Pm[h * ns + j0], zm1 = Pm[h * ns + j0 + 1], zs0 = Ps[h * ns + j0], zs1 = Ps[h * ns + j0 + 1];
         // the output factors of layer 1 and the input factors of layer 2 of these two units: in registers, under the loads above
         float b0, b1, c0, c1;
-        noisy_factor_pair(g.seed, id0 + (uint32_t)i, g.step, NZ_QB + j0, TAG_NOISY_ACT, b0, b1);
-        noisy_factor_pair(g.seed, id0 + (uint32_t)i, g.step, NZ_QC + j0, TAG_NOISY_ACT, c0, c1);
+        noisy_factor_pair(g.out.seed, id0 + (uint32_t)i, g.out.step, NZ_QB + j0, TAG_NOISY_ACT, b0, b1);
+        noisy_factor_pair(g.out.seed, id0 + (uint32_t)i, g.out.step, NZ_QC + j0, TAG_NOISY_ACT, c0, c1);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const float x = l_x[k * T + i];
@@ -195,34 +184,7 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
         noisy_logits<T, T, 4>(Pm, Ps, ns, h, M, tid, 0, l_h, l_v, l_l, LS);
     }
     __syncthreads();
-    // ---- from here on: c51_plan_kernel's lines
-    if (g.logits_out) {
-        for (int q = tid; q < M * T; q += NT) {
-            const int i = q % T, m = q / T;
-            if (i < nv) g.logits_out[(int64_t)m * g.n + e0 + i] = l_l[i * LS + m];
-        }
-        __syncthreads();
-    }
-    if (tid < na * T) {
-        const int i = tid % T, o = tid / T;
-        l_q[o * T + i] = c51_probs_q<1>(l_l + i * LS + o * n_atoms, n_atoms, g.v_min, g.delta);
-    }
-    __syncthreads();
-    if (g.probs_out) {
-        for (int q = tid; q < M * T; q += NT) {
-            const int i = q % T, m = q / T;
-            if (i < nv) g.probs_out[(int64_t)m * g.n + e0 + i] = l_l[i * LS + m];
-        }
-    }
-    if (g.q_out && tid < na * T) {
-        const int i = tid % T, o = tid / T;
-        if (i < nv) g.q_out[(int64_t)o * g.n + e0 + i] = l_q[tid];
-    }
-    if (g.actions && tid < nv) {
-        const int64_t env = e0 + tid;
-        g.actions[env] = eps_greedy_select1(StridedValues{l_q + tid, T}, NoMask{}, na, g.eps, false, g.seed, g.env_id_base + (uint32_t)env,
-                                            g.step);
-    }
+    dist_plan_tail<T, NT, LS, true>(g.out, e0, nv, na, n_atoms, l_l, l_q, [&](float* l) { return c51_probs_q<1>(l, n_atoms, g.v_min, g.delta); });
 }
 
 // ------------------------------------------------------------------------------------------------------------- fold / unfold / init
@@ -331,8 +293,15 @@ __global__ __launch_bounds__(256) void noisy_init_kernel(float* __restrict__ p, 
     p[np + q] = sigma0 / rt;
 }
 
-static bool noisy_net_ok(int64_t ns, int64_t h, int64_t M) {
-    return ns >= 2 && ns <= 16 && h >= 4 && h <= C51_HMAX && h % 4 == 0 && M >= 2 && M <= C51_MAXM;
+// the bounds of a noisy net of M output rows, stated once (dist_host.h: a list of bounds hands each one to B)
+#define NOISY_NET_BOUNDS(B, M)                                                           \
+    B(ns >= 2 && ns <= 16, "obs dim must be 2..16");                                     \
+    B(h >= 4 && h <= DIST_HMAX && h % 4 == 0, "hidden must be a multiple of 4, <= 256"); \
+    B((M) >= 2 && (M) <= DIST_MAXM, "the network has 2..256 output rows")
+
+static bool noisy_net_ok(int64_t ns, int64_t h, int64_t n_out) {
+    NOISY_NET_BOUNDS(DIST_BOUND_HOLDS, n_out);
+    return true;
 }
 
 static inline int nz_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
@@ -348,15 +317,12 @@ static inline int nz_fold_blocks(int64_t np) {
 
 using namespace rlhip;
 
-#define NOISY_REQUIRE_NET(M)                                                                        \
-    RLHIP_REQUIRE(ns >= 2 && ns <= 16, "obs dim must be 2..16");                                    \
-    RLHIP_REQUIRE(h >= 4 && h <= C51_HMAX && h % 4 == 0, "hidden must be a multiple of 4, <= 256"); \
-    RLHIP_REQUIRE((M) >= 2 && (M) <= C51_MAXM, "the network has 2..256 output rows")
+#define NOISY_REQUIRE_NET(M) NOISY_NET_BOUNDS(RLHIP_REQUIRE, M)
 
 #define NOISY_REQUIRE_SHAPE()                                                                       \
     NOISY_REQUIRE_NET(na * n_atoms);                                                                \
     RLHIP_REQUIRE(na >= 1 && na <= MAXO, "na must be 1..4");                                        \
-    RLHIP_REQUIRE(n_atoms >= 2 && n_atoms <= C51_MAXA, "n_atoms must be 2..64");                    \
+    RLHIP_REQUIRE(n_atoms >= 2 && n_atoms <= DIST_MAXK, "n_atoms must be 2..64");                    \
     RLHIP_REQUIRE(act == 0 || act == 1, "act must be 0 (relu) or 1 (tanh)");                        \
     RLHIP_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "the support needs finite v_min < v_max")
 
@@ -364,10 +330,9 @@ static int32_t noisy_plan_launch(const float* noisy, int64_t ns, int64_t h, int6
                                  float v_max, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step,
                                  int32_t* actions, float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream) {
     NoisyPlanArgs g;
-    g.noisy = noisy, g.obs = obs, g.q_out = q_out, g.probs_out = probs_out, g.logits_out = logits_out, g.actions = actions;
-    g.n = n, g.ns = (int)ns, g.h = (int)h, g.na = (int)na, g.n_atoms = (int)n_atoms;
+    g.noisy = noisy, g.obs = obs, g.out = DistPlanOut{q_out, logits_out, probs_out, actions, n, eps, seed, env_id_base, step};
+    g.ns = (int)ns, g.h = (int)h, g.na = (int)na, g.n_atoms = (int)n_atoms;
     g.v_min = v_min, g.delta = (v_max - v_min) / (float)(n_atoms - 1);
-    g.eps = eps, g.seed = seed, g.env_id_base = env_id_base, g.step = step;
     const dim3 grid((unsigned)((n + NZ_PT - 1) / NZ_PT));
     // the instantiation set: ACT in {0, 1}
     if (act == 0) hipLaunchKernelGGL((noisy_c51_plan_kernel<0, NZ_PT>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);

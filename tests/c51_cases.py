@@ -7,6 +7,7 @@ on one atom), strictly between two atoms (terminal: mass on two atoms).
 
 Axes (every value below occurs; `test_every_class_of_the_census_is_populated` counts them):
   batch    1, TILE - 1, TILE, TILE + 1, 2 TILE + 2 (TILE = 8, the gradient kernel's tile)       n_atoms  2, 3, 51, 64
+           (the planted rows go further: up to 66, and 481 .. 2059 where a workgroup takes a second tile)
   na       1, 2, 4                      ns  2, 4, 5, 16                    h  4, 64, 256            act      relu, tanh
   term     all terminal, none terminal, mixed                             n_used  -1, 0, 1, 32, 40 (cycled) or NULL
   weights  given, NULL                  double_dqn  both flags             action  one outside 0 .. na - 1
@@ -34,12 +35,12 @@ def _net(rng, ni, h, no, l1_scale=4.0):
                   rng.uniform(-0.3, 0.3, no)).astype(F32)
 
 
-def _build(name, ns, h, na, n_atoms, act, batch, seed, term="mixed", n_used=False, weights=False, double=False, bad_action=False):
+def _build(name, ns, h, na, n_atoms, act, batch, seed, term="mixed", n_used=False, weights=False, double=False, bad_action=False, l1_scale=4.0):
     rng = np.random.default_rng(seed)
     M = na * n_atoms
     c = dict(name=name, ns=ns, h=h, na=na, n_atoms=n_atoms, act=act, batch=batch, seed=seed, v_min=V_MIN, v_max=V_MAX, gamma=GAMMA,
              double=bool(double), term_mode=term)
-    c["params"] = _net(rng, ns, h, M)
+    c["params"] = _net(rng, ns, h, M, l1_scale)
     c["target"] = (c["params"] + rng.normal(0, 0.25, c["params"].shape)).astype(F32)
     c["s"] = rng.normal(0, 1, (ns, batch)).astype(F32)
     c["sn"] = rng.normal(0, 1, (ns, batch)).astype(F32)
@@ -118,6 +119,15 @@ def _spec():
             # (4 * 20800) = 201 rows at 16 -> 256 -> 64; the smallest shape meets the cap of 256 rows)
             ("second-tiles-byte-cap", dict(ns=16, h=256, na=1, n_atoms=64, act=1, batch=201 * TILE + TILE + 3, seed=9800, weights=True)),
             ("second-tiles-smallest", dict(ns=2, h=4, na=1, n_atoms=2, act=1, batch=256 * TILE + TILE + 3, seed=9900, n_used=True)),
+            # the carry with every option on: workgroup 0 reads its running sums back for a full second tile, workgroup 1 for a tile of
+            # one valid sample (258 tiles on the cap of 256 rows); 61 tiles on the 59 rows the byte cap gives the largest shape.  The
+            # GPU test asserts from the workspace size that 8 x workgroups < batch.  At 4 actions x 64 outputs x 256 units the budget
+            # of a Q value excludes about 1 % of 481 samples at the grid's layer-1 scale (no seed of 64 passes the census, ReLU or
+            # tanh); a layer 1 scaled by 0.05 instead of 4 shrinks the budget faster than the gaps, and the walk ends in two steps
+            ("carry-block-cap", dict(ns=2, h=4, na=2, n_atoms=3, act=0, batch=256 * TILE + TILE + 1, seed=9850, n_used=True, weights=True,
+                                     double=True)),
+            ("carry-byte-cap", dict(ns=16, h=256, na=4, n_atoms=64, act=1, batch=59 * TILE + TILE + 1, seed=9950, n_used=True, weights=True,
+                                    double=True, l1_scale=0.05)),
             ("all-terminal", dict(ns=3, h=64, na=2, n_atoms=51, act=0, batch=32, seed=9500, term="all")),
             ("none-terminal", dict(ns=3, h=64, na=2, n_atoms=51, act=1, batch=31, seed=9600, term="none", n_used=True))]
     return out

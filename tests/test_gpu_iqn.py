@@ -47,7 +47,11 @@ def make_net(rng, ns, h, na, nc, safe):
 #            ns  h   na nc  N   N'  batch act double seed
 GRAD = {"b1": (2, 32, 1, 2, 1, 1, 1, 0, False, 0), "b9-tanh": (4, 32, 2, 64, 5, 3, 9, 1, True, 0), "b9-wide": (16, 256, 4, 64, 5, 3, 9, 0, False, 0),
         "b9-levels": (4, 32, 3, 32, 32, 64, 9, 0, True, 0), "b67": (5, 64, 4, 6, 5, 3, 67, 0, True, 0), "b67-tanh": (3, 32, 2, 34, 3, 5, 67, 1, False, 0),
-        "multi-tile": (4, 32, 2, 4, 2, 1, 8 * 256 + 3, 0, False, 0)}  # (8 * 256 + 3: more tiles than workgroups)
+        "multi-tile": (4, 32, 2, 4, 2, 1, 8 * 256 + 3, 0, False, 0),  # (8 * 256 + 3: more tiles than workgroups)
+        # the smallest network the kernels take: the register chains carry into a full second tile (workgroup 0) and into a tile of one
+        # valid sample (workgroup 1)
+        "carry-smallest": (2, 32, 1, 2, 1, 1, 8 * 256 + 9, 0, True, 0)}
+CARRY = ("multi-tile", "carry-smallest")  # asserted below: more than one tile per workgroup
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,6 +149,9 @@ def test_gradient_against_float64_autograd(name):
     c = grad_case(name)
     ref, (ns, h, na, nc), N, Np, b = c["ref"], c["dims"], c["N"], c["Np"], c["b"]
     assert ref["zmin"] >= ZMIN and ref["margin"] >= MARGIN, f"{name}: reference decisions too close (|z| {ref['zmin']:.1e}, a* margin {ref['margin']:.1e})"
+    if name in CARRY:
+        rows = int(rl._lib.lib.rlhip_iqn_workspace_bytes(ns, h, na, nc, N, Np, b)) // (4 * (rl.iqn_nparams(ns, h, na, nc) + 1))
+        assert rows >= 1 and 8 * rows < b, f"{name}: {rows} workgroups for {b} samples: no workgroup takes a second tile"
     d = {k: torch.tensor(c[k]).cuda() for k in ("params", "target", "s", "sn", "a", "r", "term", "n_used", "weights")}
     outs = []
     for _ in range(2):

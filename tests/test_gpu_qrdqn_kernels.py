@@ -63,6 +63,11 @@ def grad(c, want=True, a=None):
 def test_gradient_against_replay_and_model(name):
     c = CC.case(name)
     rp, m, b = c["replays"]
+    if name.startswith("carry-"):
+        import rlhip as rl
+
+        rows = int(rl._lib.lib.rlhip_qrdqn_workspace_bytes(c["ns"], c["h"], c["na"], c["N"], c["batch"])) // (4 * (c["params"].size + 1))
+        assert rows >= 1 and CC.TILE * rows < c["batch"], f"{name}: {rows} workgroups for {c['batch']} samples: no workgroup takes a second tile"
     got = grad(c)
     assert np.array_equal(got["sel"], rp["sel"]), f"{name}: a* differs at {np.flatnonzero(got['sel'] != rp['sel'])}"
     worst_t = R.within(got["T"], rp["T"], b["T"], f"{name} T")

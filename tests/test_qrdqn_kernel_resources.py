@@ -1,7 +1,8 @@
 """The kernels of csrc/qrdqn.hip, read off the gfx950 code object (the recipe of tests/test_c51_kernel_resources.py).  CPU only.
 
-  the instantiation set            qrdqn_plan_kernel<ACT> and qrdqn_grad_kernel<ACT> for ACT in {0, 1}; one reduce kernel -- five kernels
-  workgroup bounds                 256 (plan: 16 envs per workgroup, thread = output row), 256 (the gradient tiles), 256 (reduce)
+  the instantiation set            qrdqn_plan_kernel<ACT> and qrdqn_grad_kernel<ACT> for ACT in {0, 1} -- four kernels (the reduce kernel:
+                                   csrc/dist.hip, tests/test_dist_kernel_resources.py)
+  workgroup bounds                 256 (plan: 16 envs per workgroup, thread = output row), 256 (the gradient tiles)
   no scratch, no spilled VGPR      every kernel; at most 256 registers (the weights in flight live in them): two workgroups per CU
   LDS                              static, sized for h = 256 and 256 rows, inside the 64 KB a kernel gets without opting in; the gradient
                                    kernel's at most 40 KB
@@ -15,7 +16,7 @@ from test_rollout_kernel_resources import LLVM, ROOT, _kernel_meta
 
 OBJ = os.path.join(ROOT, "reinforcementlearning.jl_amd", "build", "qrdqn.o")
 ACTS = [f"ILi{act}EE" for act in (0, 1)]
-KERNELS = {"qrdqn_plan_kernel": (ACTS, 256), "qrdqn_grad_kernel": (ACTS, 256), "qrdqn_reduce_kernel": ([""], 256)}
+KERNELS = {"qrdqn_plan_kernel": (ACTS, 256), "qrdqn_grad_kernel": (ACTS, 256)}
 
 
 @pytest.mark.skipif(not os.path.exists(f"{LLVM}/llvm-readelf"), reason="no llvm-readelf")
@@ -24,7 +25,7 @@ def test_qrdqn_kernels_keep_everything_in_registers_and_fit_the_lds(tmp_path):
 
     g.build()
     meta = _kernel_meta(OBJ, str(tmp_path))
-    assert len(meta) == 5, sorted(meta)
+    assert len(meta) == 4, sorted(meta)
     bad = []
     for kernel, (targs, wg) in KERNELS.items():
         mine = {k: v for k, v in meta.items() if re.search(r"\d+" + kernel + r"(I|E)", k)}
