@@ -1519,8 +1519,9 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
  * workspace: at least rlhip_c51_workspace_bytes(ns, h, na, n_atoms, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.RainbowLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ce_out: (ce + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  (NoisyDense networks: the section after IQN.)  Out of scope: a fused
- * vec-step, a gather inside the gradient launch, three-layer and bf16 nets, dueling distributional heads, sharded runs. */
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  (NoisyDense networks: the section after IQN; dueling heads: the
+ * last section, which folds them into a vector these entry points take unchanged.)  Out of scope: a fused vec-step, a gather inside the
+ * gradient launch, three-layer and bf16 nets, sharded runs. */
 int32_t rlhip_c51_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
                               float v_max, const float* obs, int64_t n, float* q_out, float* probs_out, float* logits_out,
                               rlhip_stream_t stream);
@@ -1590,8 +1591,8 @@ int32_t rlhip_c51_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_at
  *
  * One update of rlhip.QRDQNLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ql_out: (ql + eps)^alpha, written
  * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: FQF, kappa = 0 (the pure quantile loss, whose
- * gradient jumps at u = 0), NoisyDense, a fused vec-step, a gather inside the gradient launch, dueling, three-layer and bf16 nets,
- * sharded runs, UInt8 frames. */
+ * gradient jumps at u = 0), NoisyDense, a fused vec-step, a gather inside the gradient launch, three-layer and bf16 nets, sharded
+ * runs, UInt8 frames.  (Dueling heads: the last section folds them into a vector these entry points take unchanged.) */
 int32_t rlhip_qrdqn_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
                                 int64_t n, float* q_out, float* quantiles_out, rlhip_stream_t stream);
 int32_t rlhip_qrdqn_plan_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
@@ -1743,7 +1744,7 @@ int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_co
  * One update of rlhip.RainbowLearner over a NoisyApproximator = fold both nets (counter = the learner's update count) -> draw -> gather ->
  * rlhip_c51_grad_batch_f32 on the effective vectors -> [priority write-back] -> unfold -> rlhip_clip_adam_f32 on the noisy vector ->
  * target sync on the noisy vectors.  Out of scope: independent (non-factorised) noise, per-sample noise inside a batch, noisy QR-DQN /
- * IQN / scalar DQN, noisy dueling and three-layer nets, sharded runs, a fused vec-step, bf16 nets. */
+ * IQN / scalar DQN, noisy three-layer nets, sharded runs, a fused vec-step, bf16 nets.  (Noisy dueling heads: the next section.) */
 int64_t rlhip_noisy_nparams(int64_t ns, int64_t h, int64_t n_out);
 int64_t rlhip_noisy_plan_tile(void);
 int32_t rlhip_noisy_init_f32(float* params, int64_t ns, int64_t h, int64_t n_out, uint64_t seed, uint32_t net_id, float sigma0,
@@ -1758,6 +1759,72 @@ int32_t rlhip_noisy_fold_f32(const float* noisy, float* eff, const float* noisy2
                              uint64_t seed, uint32_t counter, rlhip_stream_t stream);
 int32_t rlhip_noisy_unfold_grad_f32(const float* grad_eff, float* grad_noisy, int64_t ns, int64_t h, int64_t n_out, uint64_t seed,
                                     uint32_t counter, rlhip_stream_t stream);
+
+/* --------------------------------------- dueling distributional heads (C51, QR-DQN), plain and noisy -- */
+/* (csrc/dist_dueling.hip, csrc/noisy.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * DuelingNetwork (RLCore/src/utils/networks.jl:510-522: val .+ adv .- mean(adv, dims = 1)) for a head whose value and advantage
+ * streams carry K values each -- K = n_atoms for C51, n_quantiles for QR-DQN:  l[k, o] = v[k] + a[k, o] - mean_o'(a[k, o']).  The
+ * mean runs over the actions OF EACH ATOM, which the scalar fold (rlhip_dueling_fold_f32: one mean over every head row) does not
+ * compute.  tests/dist_dueling_ref.py replays this text in numpy Float32.
+ *
+ * Dueling distributional vector: a plain mlp2(ns, h, M') vector (rlhip_mlp2_nparams / rlhip_mlp2_init_f32, unchanged) with
+ * M' = (1 + na) K output rows: rows m = k + K o, m < na K, are the advantage rows in C51's row order; rows na K + k are the K value rows.
+ * Noisy dueling vector: [ mu | sigma ] of that layout, exactly what rlhip_noisy_nparams(ns, h, M') / rlhip_noisy_init_f32 produce.
+ * rlhip_dist_dueling_nparams = rlhip_mlp2_nparams(ns, h, M'), -1 for a refused shape.
+ * Envelope: the C51 / QR-DQN envelope (ns 2..16, h a multiple of 4 and <= 256, na 1..4, K 1..64 -- 2..64 for the noisy entry points,
+ * which are C51's) and additionally M' <= 256 (na = 4, K = 51 gives 255 and is served; na = 4, K = 64 is refused).  Anything else is
+ * RLHIP_EINVAL before any launch.
+ *
+ * rlhip_dist_dueling_fold_f32 -- the dueling vector -> the EFFECTIVE plain mlp2(ns, h, na K) vector, which every C51 / QR-DQN forward,
+ * plan and gradient entry point takes unchanged (the combine is linear in the head).  W1 | b1 are copied.  Per atom k and head column
+ * j (j = h: the bias column, the same expressions), all Float32 without contraction, the order of rlhip_dueling_fold_f32:
+ *     x_o       = Wadv[k + K o, j]                       o = 0 .. na - 1
+ *     s         = ((x_0 + x_1) + x_2) + x_3              (the first na terms)
+ *     mean      = s / (float)na                          (a true division)
+ *     W2e[k + K o, j] = (Wval[k, j] + x_o) - mean
+ * The optional second pair (duel2, eff2: both or neither) is the target net, same launch.  eff must not overlap any input, eff2
+ * neither eff nor any input.
+ * rlhip_dist_dueling_unfold_grad_f32 -- the chain rule: with x_o = dW2e[k + K o, j] and s, mean as above,  dWval[k, j] = s,
+ * dWadv[k + K o, j] = x_o - mean;  gW1 | gb1 are copied.  grad_duel must not overlap grad_eff.
+ *
+ * rlhip_noisy_dueling_fold_f32 -- byte for byte rlhip_noisy_fold_f32(n_out = M') followed by rlhip_dist_dueling_fold_f32, in one
+ * launch and without the M'-row vector in between: the factors are the NoisyDense section's (tags 13 / 14, id = 0, step = counter,
+ * the same indices q; d[m'] at q = 528 + m' for every row m' < M').
+ * rlhip_noisy_dueling_unfold_grad_f32 -- byte for byte rlhip_dist_dueling_unfold_grad_f32 followed by rlhip_noisy_unfold_grad_f32(n_out
+ * = M'): grad_noisy = [ dmu | dsigma = dmu * xi ] on M' rows.
+ *
+ * rlhip_noisy_c51_dueling_forward_f32 / rlhip_noisy_c51_dueling_plan_f32 -- acting on a noisy dueling vector, one noise sample per
+ * env: the NoisyDense section's per-env lines, unchanged, on the M' rows (d[m'] at q = 528 + m') give l'[m'].  Then the combine in the
+ * OUTPUT domain, the reference's own form, per atom k:
+ *     s = ((l'[k] + l'[k + K]) + l'[k + 2 K]) + l'[k + 3 K]     (the first na terms)
+ *     mean = s / (float)na
+ *     l[k + K o] = (l'[na K + k] + l'[k + K o]) - mean
+ * then the C51 section's softmax and Q on l (the same device function), and in the plan form `actions` byte for byte
+ * rlhip_eps_greedy_select_f32 on the kernel's own q_out.  logits_out receives l (na K rows).  With sigma = 0 and every advantage row
+ * zero, l[k + K o] = l'[na K + k] exactly.  The learner's folded weights combine in the PARAMETER domain, this kernel in the output
+ * domain: the two differ by rounding only.
+ *
+ * One update of rlhip.RainbowLearner / rlhip.QRDQNLearner over a DistDuelingApproximator = the plain update on the effective vectors ->
+ * unfold -> rlhip_clip_adam_f32 on the dueling vector -> fold -> target sync on the dueling vectors (and its fold); over a
+ * NoisyDuelingApproximator (RainbowLearner only) the NoisyDense section's update with the two fused launches in the places of its fold
+ * and unfold.  Out of scope: dueling IQN, a scalar DuelingApproximator under a distributional learner, three-layer and bf16 nets,
+ * sharded runs, a fused vec-step. */
+int64_t rlhip_dist_dueling_nparams(int64_t ns, int64_t h, int64_t na, int64_t K);
+int32_t rlhip_dist_dueling_fold_f32(const float* duel, float* eff, const float* duel2, float* eff2, int64_t ns, int64_t h, int64_t na,
+                                    int64_t K, rlhip_stream_t stream);
+int32_t rlhip_dist_dueling_unfold_grad_f32(const float* grad_eff, float* grad_duel, int64_t ns, int64_t h, int64_t na, int64_t K,
+                                           rlhip_stream_t stream);
+int32_t rlhip_noisy_dueling_fold_f32(const float* noisy, float* eff, const float* noisy2, float* eff2, int64_t ns, int64_t h, int64_t na,
+                                     int64_t K, uint64_t seed, uint32_t counter, rlhip_stream_t stream);
+int32_t rlhip_noisy_dueling_unfold_grad_f32(const float* grad_eff, float* grad_noisy, int64_t ns, int64_t h, int64_t na, int64_t K,
+                                            uint64_t seed, uint32_t counter, rlhip_stream_t stream);
+int32_t rlhip_noisy_c51_dueling_forward_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act,
+                                            float v_min, float v_max, const float* obs, int64_t n, uint64_t seed, uint32_t env_id_base,
+                                            uint32_t step, float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream);
+int32_t rlhip_noisy_c51_dueling_plan_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
+                                         float v_max, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base,
+                                         uint32_t step, int32_t* actions, float* q_out, rlhip_stream_t stream);
 
 #ifdef __cplusplus
 }

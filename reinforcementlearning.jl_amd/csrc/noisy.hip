@@ -22,9 +22,18 @@
 //       plain mlp2 vector that rlhip_c51_grad_batch_f32 takes unchanged; the gradient maps back as dmu = g, dsigma = g xi, the draws
 //       REGENERATED from the key.  Every workgroup stages the ns + 2h + M factors in LDS once, then streams its elements; blockIdx.y
 //       selects the net (online / target: two Philox tags) as in the dueling fold.
+//   noisy_c51_plan_kernel<ACT, T, DUEL = true>   a noisy DUELING head (include/rlhip.h, the dueling distributional section): the same
+//       phases on M' = (1 + na) K rows -- na K advantage rows, then K value rows -- and, before dist_plan_tail, the combine in the LDS
+//       logit tile, thread = (env, atom): l[k, o] = (v[k] + a[k, o]) - mean_o' a[k, o'] (the output domain, the reference's own form)
+//   noisy_dueling_fold_kernel / noisy_dueling_unfold_kernel   the update path of a noisy dueling net, one launch each: byte for byte
+//       noisy_fold_kernel on M' rows followed by the dueling fold of dist_dueling.hip (the unfold: the reverse), without the M'-row
+//       vector in between.  Workgroups [0, l1_blocks) own W1 | b1 and stage only the a and b factors; the others own the head, stage
+//       only c and d, and give one thread one (k, j): it forms the 1 + na noisy weights fmaf(sigma, xi, mu) of its atom in registers and
+//       combines them (the unfold: dmu and dsigma = g xi of the 1 + na rows from the same registers).
 // No float atomics, no cross-lane sums: two calls on the same inputs give the same bytes.
 #include "dist_host.h"    // dist_device.h; the lists of bounds
 #include "head_device.h"  // normal_draw_pair
+#include "dist_dueling_device.h"  // the dueling combine (the DUEL axis of the plan kernel, the fused noisy dueling folds)
 
 namespace rlhip {
 
@@ -112,7 +121,7 @@ __device__ __forceinline__ void noisy_logits(const float* __restrict__ Pm, const
     }
 }
 
-template <int ACT, int T>
+template <int ACT, int T, bool DUEL = false>
 __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArgs g) {
     constexpr int NT = NZ_THREADS, LS = DIST_MAXM + 1;
     static_assert(16 * T <= NT && MAXO * T <= NT && T % 8 == 0, "thread maps of the tile; half a tile is a multiple of 4 envs");
@@ -123,7 +132,8 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
     __shared__ float l_l[T * LS];                                                  // [i][m]: d, then logits, then probabilities
     __shared__ float l_q[MAXO * T];
     const int tid = threadIdx.x;
-    const int ns = g.ns, h = g.h, na = g.na, n_atoms = g.n_atoms, M = na * n_atoms;
+    // M: the rows the network computes -- with DUEL the na K advantage rows and the K value rows (<= 256: they fit the logit tile)
+    const int ns = g.ns, h = g.h, na = g.na, n_atoms = g.n_atoms, M = (DUEL ? na + 1 : na) * n_atoms;
     const int64_t e0 = (int64_t)blockIdx.x * T;
     const int nv = (int)(g.out.n - e0 < T ? g.out.n - e0 : T);
     const uint32_t id0 = g.out.env_id_base + (uint32_t)e0;  // (wraps: the env id is a 32-bit counter word)
@@ -184,6 +194,21 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_c51_plan_kernel(NoisyPlanArg
         noisy_logits<T, T, 4>(Pm, Ps, ns, h, M, tid, 0, l_h, l_v, l_l, LS);
     }
     __syncthreads();
+    if constexpr (DUEL) {  // the combine in the logit tile, thread = (env i, atom k): the value row na K + k joins the na rows k + K o
+        for (int q = tid; q < n_atoms * T; q += NT) {
+            const int i = q % T, k = q / T;
+            float* l = l_l + i * LS + k;
+            float x[MAXO] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < na) x[o] = l[n_atoms * o];
+            dist_duel_combine(l[n_atoms * na], x, na);
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < na) l[n_atoms * o] = x[o];
+        }
+        __syncthreads();
+    }
     dist_plan_tail<T, NT, LS, true>(g.out, e0, nv, na, n_atoms, l_l, l_q, [&](float* l) { return c51_probs_q<1>(l, n_atoms, g.v_min, g.delta); });
 }
 
@@ -200,10 +225,13 @@ struct NoisyFoldArgs {
 };
 
 // f of every factor of (seed, id = 0, step = counter) under `tag` -> l_f[q], by the whole workgroup (the caller's barrier publishes them)
-__device__ __forceinline__ void noisy_stage_factors(float* l_f, int ns, int h, int M, uint64_t seed, uint32_t counter, uint32_t tag) {
+// `layers`: bit 0 the factors of layer 1 (a, b), bit 1 those of layer 2 (c, d)
+__device__ __forceinline__ void noisy_stage_factors(float* l_f, int ns, int h, int M, uint64_t seed, uint32_t counter, uint32_t tag,
+                                                    int layers = 3) {
     for (int p = threadIdx.x; p < NZ_QN / 2; p += NZ_THREADS) {
         const int q = 2 * p;
-        const bool used = q < ns || (q >= NZ_QB && q < NZ_QB + h) || (q >= NZ_QC && q < NZ_QC + h) || (q >= NZ_QD && q < NZ_QD + M);
+        const bool used = ((layers & 1) && (q < ns || (q >= NZ_QB && q < NZ_QB + h))) ||
+                          ((layers & 2) && ((q >= NZ_QC && q < NZ_QC + h) || (q >= NZ_QD && q < NZ_QD + M)));
         if (used) noisy_factor_pair(seed, 0u, counter, q, tag, l_f[q], l_f[q + 1]);
     }
 }
@@ -278,6 +306,105 @@ __global__ __launch_bounds__(NZ_THREADS) void noisy_unfold_kernel(NoisyFoldArgs 
     }
 }
 
+// ------------------------------------------------------------------------------------------- the fused noisy dueling fold / unfold
+struct NoisyDuelArgs {
+    const float* src[2];  // fold: the noisy dueling vectors [mu | sigma], M' rows;  unfold: the gradient of the effective vector, M rows
+    float* dst[2];        // fold: the effective vectors, M rows;                    unfold: the gradient [dmu | dsigma], M' rows
+    uint32_t tag[2];
+    int vec[2][3];        // 16-byte aligned: {src, src + np', dst} (fold), {src, dst, dst + np'} (unfold)
+    int npd;              // np' = mlp2_nparams(ns, h, M'): the length of one half of the noisy vector
+    int nbase;            // h ns + h: W1 | b1, at the same offset in every layout
+    int l1_blocks;        // workgroups [0, l1_blocks) own W1 | b1, the rest the head
+    int ns, h, na, K;
+    uint64_t seed;
+    uint32_t counter;
+};
+
+// the (k, j) items of the head, (h + 1) K of them (j = h: the bias column), strided over the head's workgroups
+#define NOISY_DUEL_HEAD_LOOP(g, k, j)                                                                                    \
+    for (int t_ = ((int)blockIdx.x - (g).l1_blocks) * NZ_THREADS + (int)threadIdx.x, j = t_ / (g).K, k = t_ - j * (g).K; \
+         t_ < ((g).h + 1) * (g).K; t_ += ((int)gridDim.x - (g).l1_blocks) * NZ_THREADS, j = t_ / (g).K, k = t_ - j * (g).K)
+
+// xi of row m of column j of a head: d[m] c[j] (ONE product, noisy_xi's), d[m] in the bias column
+__device__ __forceinline__ float noisy_head_xi(const float* l_f, int m, int j, int h) {
+    const float d = l_f[NZ_QD + m];
+    return j < h ? d * l_f[NZ_QC + j] : d;
+}
+
+// noisy = [mu | sigma] on M' = (1 + na) K rows -> eff on M = na K rows: fmaf(sigma, xi, mu) per element, then the dueling combine
+__global__ __launch_bounds__(NZ_THREADS) void noisy_dueling_fold_kernel(NoisyDuelArgs g) {
+    __shared__ float l_f[NZ_QN];
+    const int net = blockIdx.y;
+    const float* __restrict__ mu = g.src[net];
+    const float* __restrict__ sg = mu + g.npd;
+    float* __restrict__ eff = g.dst[net];
+    const int na = g.na, K = g.K, M = na * K, Mp = M + K;
+    const bool head = (int)blockIdx.x >= g.l1_blocks;
+    noisy_stage_factors(l_f, g.ns, g.h, Mp, g.seed, g.counter, g.tag[net], head ? 2 : 1);
+    __syncthreads();
+    if (!head) {  // W1 | b1: noisy_fold_kernel's lines on the first nbase elements
+        for (int i = 4 * ((int)blockIdx.x * NZ_THREADS + (int)threadIdx.x); i < g.nbase; i += 4 * g.l1_blocks * NZ_THREADS) {
+            const int n = g.nbase - i < 4 ? g.nbase - i : 4;
+            float m[4], s[4], e[4];
+            nz_load4(mu + i, n, g.vec[net][0], m);
+            nz_load4(sg + i, n, g.vec[net][1], s);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) e[u] = u < n ? fmaf(s[u], noisy_xi(l_f, i + u, g.ns, g.h, Mp), m[u]) : 0.f;
+            nz_store4(eff + i, n, g.vec[net][2], e);
+        }
+        return;
+    }
+    NOISY_DUEL_HEAD_LOOP(g, k, j) {
+        const int in = g.nbase + j * Mp + k;  // row k of column j; the rows of atom k are K apart, its value row is the last
+        float w[MAXO] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o)
+            if (o < na) w[o] = fmaf(sg[in + K * o], noisy_head_xi(l_f, k + K * o, j, g.h), mu[in + K * o]);
+        dist_duel_combine(fmaf(sg[in + M], noisy_head_xi(l_f, M + k, j, g.h), mu[in + M]), w, na);
+        float* out = eff + g.nbase + j * M + k;
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o)
+            if (o < na) out[K * o] = w[o];
+    }
+}
+
+// g = the gradient of eff (M rows) -> [dmu | dsigma = dmu * xi] on M' rows, the online draws regenerated
+__global__ __launch_bounds__(NZ_THREADS) void noisy_dueling_unfold_kernel(NoisyDuelArgs g) {
+    __shared__ float l_f[NZ_QN];
+    const float* __restrict__ ge = g.src[0];
+    float* __restrict__ dmu = g.dst[0];
+    float* __restrict__ dsg = dmu + g.npd;
+    const int na = g.na, K = g.K, M = na * K, Mp = M + K;
+    const bool head = (int)blockIdx.x >= g.l1_blocks;
+    noisy_stage_factors(l_f, g.ns, g.h, Mp, g.seed, g.counter, g.tag[0], head ? 2 : 1);
+    __syncthreads();
+    if (!head) {  // gW1 | gb1: noisy_unfold_kernel's lines on the first nbase elements
+        for (int i = 4 * ((int)blockIdx.x * NZ_THREADS + (int)threadIdx.x); i < g.nbase; i += 4 * g.l1_blocks * NZ_THREADS) {
+            const int n = g.nbase - i < 4 ? g.nbase - i : 4;
+            float v[4], d[4];
+            nz_load4(ge + i, n, g.vec[0][0], v);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) d[u] = u < n ? v[u] * noisy_xi(l_f, i + u, g.ns, g.h, Mp) : 0.f;
+            nz_store4(dmu + i, n, g.vec[0][1], v);
+            nz_store4(dsg + i, n, g.vec[0][2], d);
+        }
+        return;
+    }
+    NOISY_DUEL_HEAD_LOOP(g, k, j) {
+        const float* in = ge + g.nbase + j * M + k;
+        float x[MAXO] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o)
+            if (o < na) x[o] = in[K * o];
+        const float s = dist_duel_uncombine(x, na);
+        const int out = g.nbase + j * Mp + k;
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o)
+            if (o < na) dmu[out + K * o] = x[o], dsg[out + K * o] = x[o] * noisy_head_xi(l_f, k + K * o, j, g.h);
+        dmu[out + M] = s, dsg[out + M] = s * noisy_head_xi(l_f, M + k, j, g.h);
+    }
+}
+
 // mu = (2 u - 1) / sqrt(fan_in), sigma = sigma0 / sqrt(fan_in); u by the rule of mlp2_init_kernel, tensor ids 0: W1, 1: b1, 2: W2, 3: b2
 __global__ __launch_bounds__(256) void noisy_init_kernel(float* __restrict__ p, int ns, int h, int M, uint64_t seed, uint32_t net_id,
                                                          float sigma0) {
@@ -326,16 +453,34 @@ using namespace rlhip;
     RLHIP_REQUIRE(act == 0 || act == 1, "act must be 0 (relu) or 1 (tanh)");                        \
     RLHIP_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "the support needs finite v_min < v_max")
 
+// a noisy dueling C51 net: K = n_atoms in 2..64, (1 + na) K <= 256 rows
+#define NOISY_REQUIRE_DUEL_SHAPE()                                                                  \
+    DIST_DUEL_BOUNDS(RLHIP_REQUIRE, 2);                                                             \
+    RLHIP_REQUIRE(act == 0 || act == 1, "act must be 0 (relu) or 1 (tanh)");                        \
+    RLHIP_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "the support needs finite v_min < v_max")
+
+// the arguments of a fused noisy dueling launch and its grid: l1_blocks workgroups for W1 | b1, then the head's
+static int noisy_duel_args(NoisyDuelArgs& g, int64_t ns, int64_t h, int64_t na, int64_t K, uint64_t seed, uint32_t counter) {
+    g.npd = (int)mlp2_nparams(ns, h, (1 + na) * K), g.nbase = (int)(h * ns + h);
+    g.ns = (int)ns, g.h = (int)h, g.na = (int)na, g.K = (int)K, g.seed = seed, g.counter = counter;
+    g.l1_blocks = nz_fold_blocks(g.nbase);
+    return g.l1_blocks + nz_fold_blocks(4 * (h + 1) * K);  // (a head thread owns one (k, j), not a quad)
+}
+
 static int32_t noisy_plan_launch(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
                                  float v_max, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base, uint32_t step,
-                                 int32_t* actions, float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream) {
+                                 int32_t* actions, float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream,
+                                 bool duel = false) {
     NoisyPlanArgs g;
     g.noisy = noisy, g.obs = obs, g.out = DistPlanOut{q_out, logits_out, probs_out, actions, n, eps, seed, env_id_base, step};
     g.ns = (int)ns, g.h = (int)h, g.na = (int)na, g.n_atoms = (int)n_atoms;
     g.v_min = v_min, g.delta = (v_max - v_min) / (float)(n_atoms - 1);
     const dim3 grid((unsigned)((n + NZ_PT - 1) / NZ_PT));
-    // the instantiation set: ACT in {0, 1}
-    if (act == 0) hipLaunchKernelGGL((noisy_c51_plan_kernel<0, NZ_PT>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);
+    // the instantiation set: ACT in {0, 1} x DUEL in {false, true}
+    if (duel) {
+        if (act == 0) hipLaunchKernelGGL((noisy_c51_plan_kernel<0, NZ_PT, true>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);
+        else hipLaunchKernelGGL((noisy_c51_plan_kernel<1, NZ_PT, true>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);
+    } else if (act == 0) hipLaunchKernelGGL((noisy_c51_plan_kernel<0, NZ_PT>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);
     else hipLaunchKernelGGL((noisy_c51_plan_kernel<1, NZ_PT>), grid, dim3(NZ_THREADS), 0, as_stream(stream), g);
     RLHIP_LAUNCH_CHECK();
     return RLHIP_OK;
@@ -420,6 +565,72 @@ int32_t rlhip_noisy_unfold_grad_f32(const float* grad_eff, float* grad_noisy, in
     g.vec[0][0] = nz_aligned16(grad_eff), g.vec[0][1] = nz_aligned16(grad_noisy), g.vec[0][2] = nz_aligned16(grad_noisy + np);
     g.vec[1][0] = g.vec[1][1] = g.vec[1][2] = 0;
     hipLaunchKernelGGL(noisy_unfold_kernel, dim3(nz_fold_blocks(np)), dim3(NZ_THREADS), 0, as_stream(stream), g);
+    RLHIP_LAUNCH_CHECK();
+    return RLHIP_OK;
+}
+
+// ---- noisy dueling heads (include/rlhip.h, the dueling distributional section)
+int32_t rlhip_noisy_c51_dueling_forward_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act,
+                                            float v_min, float v_max, const float* obs, int64_t n, uint64_t seed, uint32_t env_id_base,
+                                            uint32_t step, float* q_out, float* probs_out, float* logits_out, rlhip_stream_t stream) {
+    const int64_t K = n_atoms;
+    NOISY_REQUIRE_DUEL_SHAPE();
+    RLHIP_REQUIRE(n >= 0 && n <= 0x7fffffffLL, "env count must be 0 .. 2^31 - 1");
+    RLHIP_REQUIRE(noisy && obs && q_out, "NULL argument");
+    if (n == 0) return RLHIP_OK;
+    return noisy_plan_launch(noisy, ns, h, na, n_atoms, act, v_min, v_max, obs, n, 0.0, seed, env_id_base, step, nullptr, q_out, probs_out,
+                             logits_out, stream, true);
+}
+
+int32_t rlhip_noisy_c51_dueling_plan_f32(const float* noisy, int64_t ns, int64_t h, int64_t na, int64_t n_atoms, int32_t act, float v_min,
+                                         float v_max, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base,
+                                         uint32_t step, int32_t* actions, float* q_out, rlhip_stream_t stream) {
+    const int64_t K = n_atoms;
+    NOISY_REQUIRE_DUEL_SHAPE();
+    RLHIP_REQUIRE(n >= 0 && n <= 0x7fffffffLL, "env count must be 0 .. 2^31 - 1");
+    RLHIP_REQUIRE(noisy && obs && actions, "NULL argument");
+    if (n == 0) return RLHIP_OK;
+    return noisy_plan_launch(noisy, ns, h, na, n_atoms, act, v_min, v_max, obs, n, eps, seed, env_id_base, step, actions, q_out, nullptr,
+                             nullptr, stream, true);
+}
+
+int32_t rlhip_noisy_dueling_fold_f32(const float* noisy, float* eff, const float* noisy2, float* eff2, int64_t ns, int64_t h, int64_t na,
+                                     int64_t K, uint64_t seed, uint32_t counter, rlhip_stream_t stream) {
+    DIST_DUEL_BOUNDS(RLHIP_REQUIRE, 2);
+    RLHIP_REQUIRE(noisy && eff, "NULL argument");
+    RLHIP_REQUIRE((noisy2 == nullptr) == (eff2 == nullptr), "the second net is a pair: both noisy2 and eff2, or neither");
+    NoisyDuelArgs g;
+    const int blocks = noisy_duel_args(g, ns, h, na, K, seed, counter);
+    const int64_t npd = g.npd, ne = mlp2_nparams(ns, h, na * K);
+    RLHIP_REQUIRE(!nz_overlap(eff, ne, noisy, 2 * npd), "eff must not overlap the noisy vector");
+    RLHIP_REQUIRE(!noisy2 || (!nz_overlap(eff2, ne, noisy2, 2 * npd) && !nz_overlap(eff2, ne, eff, ne) &&
+                              !nz_overlap(eff2, ne, noisy, 2 * npd) && !nz_overlap(eff, ne, noisy2, 2 * npd)),
+                  "the second pair must not overlap the first pair's output or its own input");
+    g.src[0] = noisy, g.dst[0] = eff, g.tag[0] = TAG_NOISY_ONLINE;
+    g.src[1] = noisy2, g.dst[1] = eff2, g.tag[1] = TAG_NOISY_TARGET;
+    for (int k = 0; k < 2; ++k) {
+        g.vec[k][0] = g.src[k] ? nz_aligned16(g.src[k]) : 0;
+        g.vec[k][1] = g.src[k] ? nz_aligned16(g.src[k] + npd) : 0;
+        g.vec[k][2] = g.dst[k] ? nz_aligned16(g.dst[k]) : 0;
+    }
+    hipLaunchKernelGGL(noisy_dueling_fold_kernel, dim3(blocks, noisy2 ? 2 : 1), dim3(NZ_THREADS), 0, as_stream(stream), g);
+    RLHIP_LAUNCH_CHECK();
+    return RLHIP_OK;
+}
+
+int32_t rlhip_noisy_dueling_unfold_grad_f32(const float* grad_eff, float* grad_noisy, int64_t ns, int64_t h, int64_t na, int64_t K,
+                                            uint64_t seed, uint32_t counter, rlhip_stream_t stream) {
+    DIST_DUEL_BOUNDS(RLHIP_REQUIRE, 2);
+    RLHIP_REQUIRE(grad_eff && grad_noisy, "NULL argument");
+    NoisyDuelArgs g;
+    const int blocks = noisy_duel_args(g, ns, h, na, K, seed, counter);
+    const int64_t npd = g.npd;
+    RLHIP_REQUIRE(!nz_overlap(grad_noisy, 2 * npd, grad_eff, mlp2_nparams(ns, h, na * K)), "grad_noisy must not overlap grad_eff");
+    g.src[0] = grad_eff, g.dst[0] = grad_noisy, g.tag[0] = TAG_NOISY_ONLINE;
+    g.src[1] = nullptr, g.dst[1] = nullptr, g.tag[1] = 0;
+    g.vec[0][0] = nz_aligned16(grad_eff), g.vec[0][1] = nz_aligned16(grad_noisy), g.vec[0][2] = nz_aligned16(grad_noisy + npd);
+    g.vec[1][0] = g.vec[1][1] = g.vec[1][2] = 0;
+    hipLaunchKernelGGL(noisy_dueling_unfold_kernel, dim3(blocks), dim3(NZ_THREADS), 0, as_stream(stream), g);
     RLHIP_LAUNCH_CHECK();
     return RLHIP_OK;
 }

@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner, HipNoisyApproximator
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner, HipNoisyApproximator, HipDistDuelingApproximator
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2445,6 +2445,100 @@ function noisy_plan!(actions::DevBuf{Int32}, A::HipNoisyApproximator, n_actions,
               (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32,
                Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
               A.noisy.ptr, A.n_in, A.hidden, n_actions, n_atoms, A.act, v_min, v_max, obs.ptr, n, ϵ, seed, env_id_base, step,
+              actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
+    actions
+end
+
+# -------------------------------------------------------------------------------------------- dueling distributional heads
+# The ccalls of csrc/dist_dueling.hip and the dueling entry points of csrc/noisy.hip (include/rlhip.h, "dueling distributional heads"):
+# per atom k, l[k, o] = v[k] + a[k, o] - mean over the actions of a[k, :].  The trained vector is a plain two-layer vector with
+# (1 + n_actions) * n_atoms output rows; `params` is its fold, the effective vector the C51 / QR-DQN entry points take unchanged.
+
+"FluxApproximator(model = DuelingNetwork(base, val = Dense(h, n_atoms), adv = Dense(h, n_actions * n_atoms)), optimiser = Adam(lr));
+`dueling` is the trained vector, `params` the effective plain vector, `m` / `v` / `grad` have the dueling length"
+mutable struct HipDistDuelingApproximator <: AbstractLearner
+    n_in::Int; hidden::Int; n_actions::Int; n_atoms::Int; act::Int32
+    dueling::DevBuf{Float32}; params::DevBuf{Float32}; grad::DevBuf{Float32}
+    m::DevBuf{Float32}; v::DevBuf{Float32}; beta_pow::DevBuf{Float32}; gn::DevBuf{Float32}
+    lr::Float32; beta1::Float32; beta2::Float32; eps::Float32
+end
+function HipDistDuelingApproximator(n_in, hidden, n_actions, n_atoms; act = 0, lr = 1f-3, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8,
+                                    seed = 0, net_id = 0)
+    nd = ccall((:rlhip_dist_dueling_nparams, LIB), Int64, (Int64, Int64, Int64, Int64), n_in, hidden, n_actions, n_atoms)
+    nd > 0 || throw(ArgumentError("HipDistDuelingApproximator: obs_dim 2..16, hidden a multiple of 4 and <= 256, 1..4 actions, " *
+                                  "(1 + n_actions) * n_atoms <= 256"))
+    ne = ccall((:rlhip_mlp2_nparams, LIB), Int64, (Int64, Int64, Int64), n_in, hidden, n_actions * n_atoms)
+    p = DevBuf{Float32}(nd)
+    chk(ccall((:rlhip_mlp2_init_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              p.ptr, n_in, hidden, (1 + n_actions) * n_atoms, seed, net_id, stream()))
+    A = HipDistDuelingApproximator(n_in, hidden, n_actions, n_atoms, act, p, DevBuf{Float32}(ne), DevBuf{Float32}(nd), DevBuf{Float32}(nd),
+                                   DevBuf{Float32}(nd), to_dev!(DevBuf{Float32}(2), Float32[beta1, beta2]), DevBuf{Float32}(1), lr, beta1,
+                                   beta2, eps)
+    refold!(A)
+    A
+end
+
+"dueling distributional vector -> effective plain vector, one launch; (duel2, eff2): an optional second net (the target) in the same launch"
+function fold_dist_dueling!(eff::DevBuf{Float32}, duel::DevBuf{Float32}, n_in, hidden, n_actions, n_atoms; duel2 = nothing, eff2 = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_dist_dueling_fold_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Cvoid}),
+              duel.ptr, eff.ptr, np(duel2), np(eff2), n_in, hidden, n_actions, n_atoms, stream()))
+    eff
+end
+"A.params from A.dueling"
+refold!(A::HipDistDuelingApproximator) = (fold_dist_dueling!(A.params, A.dueling, A.n_in, A.hidden, A.n_actions, A.n_atoms); A)
+
+"`grad`: the gradient of `params` as the plain kernels wrote it -> the dueling gradient, clip + Adam on the dueling vector, fold again"
+function optimise!(A::HipDistDuelingApproximator, grad::DevBuf{Float32}; clip_norm = 0f0, grad_scale = 1f0)
+    chk(ccall((:rlhip_dist_dueling_unfold_grad_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Cvoid}),
+              grad.ptr, A.grad.ptr, A.n_in, A.hidden, A.n_actions, A.n_atoms, stream()))
+    chk(ccall((:rlhip_clip_adam_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Float32,
+               Float32, Ptr{Cvoid}, Ptr{Cvoid}),
+              A.dueling.ptr, A.grad.ptr, A.m.ptr, A.v.ptr, A.beta_pow.ptr, A.dueling.n, grad_scale, clip_norm, A.lr, A.beta1,
+              A.beta2, A.eps, A.gn.ptr, stream()))
+    refold!(A)
+end
+
+"noisy dueling vector [μ | σ] on (1 + n_actions) * n_atoms rows -> effective plain vector: noise and combine in one launch"
+function fold_noisy_dueling!(eff::DevBuf{Float32}, noisy::DevBuf{Float32}, n_in, hidden, n_actions, n_atoms, seed, counter;
+                             noisy2 = nothing, eff2 = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_noisy_dueling_fold_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              noisy.ptr, eff.ptr, np(noisy2), np(eff2), n_in, hidden, n_actions, n_atoms, seed, counter, stream()))
+    eff
+end
+
+"gradient of the effective vector -> [dμ | dσ] of the noisy dueling vector, the draws of (seed, counter) regenerated, one launch"
+function unfold_noisy_dueling_grad!(grad_noisy::DevBuf{Float32}, grad_eff::DevBuf{Float32}, n_in, hidden, n_actions, n_atoms, seed, counter)
+    chk(ccall((:rlhip_noisy_dueling_unfold_grad_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              grad_eff.ptr, grad_noisy.ptr, n_in, hidden, n_actions, n_atoms, seed, counter, stream()))
+    grad_noisy
+end
+
+"noisy_forward! on a noisy dueling vector (one noise sample per env, the combine in the output domain)"
+function noisy_dueling_forward!(q::DevBuf{Float32}, noisy::DevBuf{Float32}, n_in, hidden, n_actions, n_atoms, act, v_min, v_max,
+                                obs::DevBuf{Float32}, n; seed = UInt64(0), env_id_base = UInt32(0), step = UInt32(0), probs = nothing,
+                                logits = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_noisy_c51_dueling_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              noisy.ptr, n_in, hidden, n_actions, n_atoms, act, v_min, v_max, obs.ptr, n, seed, env_id_base, step, q.ptr,
+              np(probs), np(logits), stream()))
+    q
+end
+
+"plan! in one launch: byte for byte noisy_dueling_forward! followed by the EpsilonGreedyExplorer's selection (no tie-break)"
+function noisy_dueling_plan!(actions::DevBuf{Int32}, noisy::DevBuf{Float32}, n_in, hidden, n_actions, n_atoms, act, v_min, v_max,
+                             obs::DevBuf{Float32}, n, ϵ; seed = UInt64(0), env_id_base = UInt32(0), step = UInt32(0), q = nothing)
+    chk(ccall((:rlhip_noisy_c51_dueling_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              noisy.ptr, n_in, hidden, n_actions, n_atoms, act, v_min, v_max, obs.ptr, n, ϵ, seed, env_id_base, step,
               actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
     actions
 end

@@ -356,6 +356,13 @@ _PROTOS = {
     "rlhip_noisy_c51_plan_f32": (i32, [vp, i64, i64, i64, i64, i32, f32, f32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
     "rlhip_noisy_fold_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, u64, u32, vp]),
     "rlhip_noisy_unfold_grad_f32": (i32, [vp, vp, i64, i64, i64, u64, u32, vp]),
+    "rlhip_dist_dueling_nparams": (i64, [i64, i64, i64, i64]),
+    "rlhip_dist_dueling_fold_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+    "rlhip_dist_dueling_unfold_grad_f32": (i32, [vp, vp, i64, i64, i64, i64, vp]),
+    "rlhip_noisy_dueling_fold_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, u64, u32, vp]),
+    "rlhip_noisy_dueling_unfold_grad_f32": (i32, [vp, vp, i64, i64, i64, i64, u64, u32, vp]),
+    "rlhip_noisy_c51_dueling_forward_f32": (i32, [vp, i64, i64, i64, i64, i32, f32, f32, vp, i64, u64, u32, u32, vp, vp, vp, vp]),
+    "rlhip_noisy_c51_dueling_plan_f32": (i32, [vp, i64, i64, i64, i64, i32, f32, f32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
 }
 
 _STATUS = set()

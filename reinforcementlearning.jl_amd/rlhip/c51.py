@@ -9,7 +9,11 @@ row k + n_atoms * o = atom k of action o.
 NoisyDense networks: RainbowLearner over TargetNetwork(NoisyApproximator(...)) (rlhip/noisy.py) -- plan!, forward and distribution draw
 an independent noise sample per env from the noisy vector; every update folds fresh online and target noise first.
 
-Out of scope, refused by name: a fused vec-step, three-layer and bf16 networks, dueling distributional heads, sharded runs
+Dueling heads: RainbowLearner over TargetNetwork(DistDuelingApproximator(...)) or, with NoisyDense layers,
+TargetNetwork(NoisyDuelingApproximator(...)) (rlhip/dist_dueling.py) -- the combine is folded into the effective vector the kernels read;
+a noisy dueling net acts through rlhip_noisy_c51_dueling_plan_f32.
+
+Out of scope, refused by name: a fused vec-step, three-layer and bf16 networks, a scalar DuelingApproximator, sharded runs
 (world > 1), UInt8 frames.
 """
 import torch
@@ -17,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import call
 from .dqn import DQNLearner, _Scratch, refuse_noisy
+from .dist_dueling import noisy_c51_dueling_forward, noisy_c51_dueling_plan
 from .noisy import noisy_c51_forward, noisy_c51_plan
 from .ops import ptr, stream_ptr
 
@@ -91,9 +96,12 @@ class DistributionalLearner(DQNLearner):
             refuse_noisy(net, name)
         elif getattr(net, "noisy_params", None) is not None and process_group is not None:
             raise NotImplementedError(f"{name}: a NoisyApproximator with a process group (a sharded run) is out of scope")
-        if getattr(net, "dueling_params", None) is not None:
-            raise NotImplementedError(f"{name}: a DuelingApproximator (dueling distributional heads) is out of scope; use a "
-                                      "HipApproximator")
+        if getattr(net, "dueling_params", None) is not None and not getattr(net, "dist_dueling", False):
+            raise NotImplementedError(f"{name}: a DuelingApproximator folds ONE mean over every head row, a distributional head needs the "
+                                      "mean over the actions of each atom; use a DistDuelingApproximator (or a plain HipApproximator)")
+        if getattr(net, "dist_dueling", False) and (net.n_actions, net.n_atoms) != (n_actions, n_rows):
+            raise ValueError(f"{name}: the dueling network has n_actions = {net.n_actions}, n_atoms = {net.n_atoms}; the learner "
+                             f"n_actions = {n_actions}, {rows} = {n_rows}")
         if getattr(net, "layers", 2) == 3:
             raise NotImplementedError(f"{name}: three-layer (layers = 3, bf16 MFMA) networks are out of scope; use a two-layer "
                                       "HipApproximator (layers = 2)")
@@ -202,6 +210,13 @@ class RainbowLearner(DistributionalLearner):
     def _noisy(self):
         return getattr(self.approximator.network, "noisy_params", None) is not None
 
+    @property
+    def _noisy_entries(self):
+        """(forward, plan) of the noisy network: a noisy dueling head combines inside its own launches"""
+        if getattr(self.approximator.network, "dist_dueling", False):
+            return noisy_c51_dueling_forward, noisy_c51_dueling_plan
+        return noisy_c51_forward, noisy_c51_plan
+
     def _forward_key(self, seed, step):
         """(seed, step) of a noisy forward outside plan!: without them every call draws new noise"""
         if step is None:
@@ -213,7 +228,7 @@ class RainbowLearner(DistributionalLearner):
         NoisyApproximator's per-env noise"""
         if self._noisy:
             seed, step = self._forward_key(seed, step)
-            return noisy_c51_forward(*self._noisy_args(), x, seed, env_id_base, step)
+            return self._noisy_entries[0](*self._noisy_args(), x, seed, env_id_base, step)
         return c51_forward(*self._net_args(), x)
 
     def distribution(self, x, seed=None, env_id_base=0, step=None):
@@ -221,7 +236,7 @@ class RainbowLearner(DistributionalLearner):
         probs = torch.empty((self.n_actions * self.n_atoms, x.shape[1]), dtype=torch.float32, device=x.device)
         if self._noisy:
             seed, step = self._forward_key(seed, step)
-            q = noisy_c51_forward(*self._noisy_args(), x, seed, env_id_base, step, probs=probs)
+            q = self._noisy_entries[0](*self._noisy_args(), x, seed, env_id_base, step, probs=probs)
         else:
             q = c51_forward(*self._net_args(), x, probs=probs)
         return q, probs.view(self.n_actions, self.n_atoms, -1).permute(1, 0, 2)
@@ -231,7 +246,7 @@ class RainbowLearner(DistributionalLearner):
         if q_out is not None and q_out.shape[0] != self.n_actions:
             q_out = None
         if self._noisy:
-            return noisy_c51_plan(*self._noisy_args(), obs, eps, seed, env_id_base, step, actions, q_out)
+            return self._noisy_entries[1](*self._noisy_args(), obs, eps, seed, env_id_base, step, actions, q_out)
         return c51_plan(*self._net_args(), obs, eps, seed, env_id_base, step, actions, q_out)
 
     # -------------------------------------------------------------------------------- optimise!

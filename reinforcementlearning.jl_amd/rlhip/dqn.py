@@ -338,7 +338,8 @@ class DuelingApproximator(HipApproximator):
 class TargetNetwork:
     """TargetNetwork(network; sync_freq = 1, ρ = 0f0)  target_network.jl:27-60.  With a DuelingApproximator the target is kept as a
     dueling vector too (`target_dueling`): Polyak runs on the dueling vectors and `target`, the effective vector, is folded again.
-    With a NoisyApproximator likewise (`target_noisy`); `target` is then written by the learner's next `resample_`, under fresh noise."""
+    With a NoisyApproximator likewise (`target_noisy`); `target` is then written by the learner's next `resample_`, under fresh noise.
+    A DistDuelingApproximator / NoisyDuelingApproximator (rlhip/dist_dueling.py) is kept the same way, by the same two attributes."""
 
     def __init__(self, network, sync_freq=1, rho=0.0):
         if not 0 <= rho <= 1:
@@ -365,7 +366,10 @@ class TargetNetwork:
             net = self.network
             if getattr(net, "dueling_params", None) is not None:
                 polyak_(self.target_dueling, net.dueling_params, self.rho)
-                fold_dueling(self.target_dueling, self.target, net.n_in, net.hidden, net.n_out, getattr(net, "layers", 2))
+                if getattr(net, "dist_dueling", False):  # a DistDuelingApproximator: the per-atom fold of csrc/dist_dueling.hip
+                    net.fold_(self.target_dueling, self.target)
+                else:
+                    fold_dueling(self.target_dueling, self.target, net.n_in, net.hidden, net.n_out, getattr(net, "layers", 2))
             elif getattr(net, "noisy_params", None) is not None:
                 polyak_(self.target_noisy, net.noisy_params, self.rho)
             else:

@@ -6,8 +6,9 @@ Acting draws an independent noise sample per env inside the plan launch (rlhip_n
 dueling idiom: one sample per update and net is folded into a plain vector (rlhip_noisy_fold_f32), the unchanged C51 gradient runs on it,
 and the gradient is mapped back with the regenerated draws (rlhip_noisy_unfold_grad_f32).
 
-Out of scope, refused by name: independent noise, per-sample noise inside a batch, noisy QR-DQN / IQN / scalar DQN, noisy dueling and
-three-layer nets, sharded runs, a fused vec-step, bf16 nets.
+Out of scope, refused by name: independent noise, per-sample noise inside a batch, noisy QR-DQN / IQN / scalar DQN, noisy
+three-layer nets, sharded runs, a fused vec-step, bf16 nets.  A noisy dueling head is a class of its own, NoisyDuelingApproximator
+(rlhip/dist_dueling.py): this one keeps its plain head.
 """
 import torch
 
@@ -71,8 +72,8 @@ class NoisyApproximator(HipApproximator):
     def __init__(self, n_in, hidden, n_out, act="relu", lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0, net_id=0, device="cuda",
                  sigma0=0.5, noisy_params=None, layers=2, dueling=False):
         if layers != 2 or dueling:
-            raise NotImplementedError("NoisyApproximator: two-layer plain heads only; noisy three-layer (layers = 3) and noisy dueling "
-                                      "networks are out of scope")
+            raise NotImplementedError("NoisyApproximator: two-layer plain heads only; noisy three-layer (layers = 3) networks are out of "
+                                      "scope, a noisy dueling head is rlhip.NoisyDuelingApproximator")
         nn = noisy_nparams(n_in, hidden, n_out)
         if nn < 0:
             raise ValueError(f"NoisyApproximator: the noisy kernels take {ENVELOPE}; got n_in = {n_in}, hidden = {hidden}, n_out = {n_out}")

@@ -440,6 +440,31 @@ def noisy_unfold_grad(grad_eff, grad_noisy, n_in, h, n_out, seed, counter):
     return grad_noisy
 
 
+def dist_dueling_fold(duel, eff, n_in, h, na, K, duel2=None, eff2=None):
+    """dueling distributional vector(s), mlp2(n_in, h, (1 + na) K) -> effective plain vector(s), mlp2(n_in, h, na K), one launch
+    (csrc/dist_dueling.hip); the second pair is the target net"""
+    call("rlhip_dist_dueling_fold_f32", ptr(duel), ptr(eff), ptr(duel2), ptr(eff2), n_in, h, na, K, stream_ptr())
+    return eff
+
+
+def dist_dueling_unfold_grad(grad_eff, grad_duel, n_in, h, na, K):
+    """gradient of the effective vector -> gradient of the dueling distributional vector (the chain rule of the fold), one launch"""
+    call("rlhip_dist_dueling_unfold_grad_f32", ptr(grad_eff), ptr(grad_duel), n_in, h, na, K, stream_ptr())
+    return grad_duel
+
+
+def noisy_dueling_fold(noisy, eff, n_in, h, na, K, seed, counter, noisy2=None, eff2=None):
+    """byte for byte `noisy_fold` (n_out = (1 + na) K) then `dist_dueling_fold`, in one launch"""
+    call("rlhip_noisy_dueling_fold_f32", ptr(noisy), ptr(eff), ptr(noisy2), ptr(eff2), n_in, h, na, K, seed, counter, stream_ptr())
+    return eff
+
+
+def noisy_dueling_unfold_grad(grad_eff, grad_noisy, n_in, h, na, K, seed, counter):
+    """byte for byte `dist_dueling_unfold_grad` then `noisy_unfold_grad` (n_out = (1 + na) K), in one launch"""
+    call("rlhip_noisy_dueling_unfold_grad_f32", ptr(grad_eff), ptr(grad_noisy), n_in, h, na, K, seed, counter, stream_ptr())
+    return grad_noisy
+
+
 def fill_uniform(n, seed, t, tag, device="cuda"):
     out = torch.empty(n, dtype=torch.float32, device=device)
     call("rlhip_fill_uniform_f32", ptr(out), n, seed, t, tag, stream_ptr())

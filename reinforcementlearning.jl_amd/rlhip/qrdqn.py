@@ -5,8 +5,10 @@ levels tau_k = (2 k + 1) / (2 N), fitted by the quantile-Huber loss (Dabney et a
 reference snapshot, so include/rlhip.h states the update (csrc/qrdqn.hip implements it, tests/qrdqn_ref.py replays it).  The network is
 the shipped two-layer layout with n_actions * n_quantiles output rows, row k + n_quantiles * o = quantile k of action o.
 
-Out of scope, refused by name: FQF, kappa = 0, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling
-distributional heads, sharded runs (world > 1), UInt8 frames.
+Dueling heads: QRDQNLearner over TargetNetwork(DistDuelingApproximator(ns, h, n_actions, n_quantiles)) (rlhip/dist_dueling.py).
+
+Out of scope, refused by name: FQF, kappa = 0, NoisyDense (a NoisyDuelingApproximator too), a fused vec-step, three-layer and bf16
+networks, a scalar DuelingApproximator, sharded runs (world > 1), UInt8 frames.
 """
 import math
 
