@@ -1590,7 +1590,7 @@ int32_t rlhip_c51_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_at
  * workspace: at least rlhip_qrdqn_workspace_bytes(ns, h, na, N, batch) bytes (-1 for a refused shape); no initialisation.
  *
  * One update of rlhip.QRDQNLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ql_out: (ql + eps)^alpha, written
- * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: FQF, kappa = 0 (the pure quantile loss, whose
+ * back under the drawn keys] -> rlhip_clip_adam_f32 -> target sync.  (FQF: its own section below.)  Out of scope: kappa = 0 (the pure quantile loss, whose
  * gradient jumps at u = 0), NoisyDense, a fused vec-step, a gather inside the gradient launch, three-layer and bf16 nets, sharded
  * runs, UInt8 frames.  (Dueling heads: the last section folds them into a vector these entry points take unchanged.) */
 int32_t rlhip_qrdqn_forward_f32(const float* params, int64_t ns, int64_t h, int64_t na, int64_t n_quantiles, int32_t act, const float* obs,
@@ -1672,7 +1672,7 @@ int32_t rlhip_qrdqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_
  * workspace: at least rlhip_iqn_workspace_bytes(ns, h, na, n_cos, N, N', batch) bytes; no initialisation.
  *
  * One update of rlhip.IQNLearner = draw -> gather -> this gradient (seed = the learner's, draw_ctr = its draw counter) ->
- * [rlhip_per_priority_f32 on ql_out] -> rlhip_clip_adam_f32 -> target sync.  Out of scope: FQF, kappa = 0, NoisyDense, a fused vec-step,
+ * [rlhip_per_priority_f32 on ql_out] -> rlhip_clip_adam_f32 -> target sync.  (FQF: the next section.)  Out of scope: kappa = 0, NoisyDense, a fused vec-step,
  * dueling, three-layer and bf16 nets, sharded runs, UInt8 frames, the bounds-checked build's action check. */
 int64_t rlhip_iqn_nparams(int64_t ns, int64_t h, int64_t na, int64_t n_cos);
 int32_t rlhip_iqn_init_f32(float* params, int64_t ns, int64_t h, int64_t na, int64_t n_cos, uint64_t seed, uint32_t net_id,
@@ -1691,6 +1691,77 @@ int32_t rlhip_iqn_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_co
                                  const float* weights, int32_t double_dqn, uint64_t seed, uint32_t draw_ctr, void* workspace,
                                  float* grad_out, float* loss_out, float* ql_out, float* target_out, int32_t* sel_out, float* tau_out,
                                  float* tau_target_out, rlhip_stream_t stream);
+
+/* ------------------------------- fully parameterised quantile function (FQF) distributional DQN learner -- */
+/* (csrc/fqf.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * Yang et al. 2019, "Fully Parameterized Quantile Function for Distributional RL": the quantile levels are neither fixed (QR-DQN) nor
+ * drawn (IQN) but PLACED by a fraction-proposal network on the state embedding.  Not in the reference snapshot: THIS TEXT is the
+ * specification (tests/fqf_ref.py states the mathematics in Float64).
+ *
+ * Quantile network: the ImplicitQuantileNet of the IQN section, same flat layout, rlhip_iqn_nparams and rlhip_iqn_init_f32.
+ * Fraction network: a SECOND flat vector  Wf (N x h, column-major as mlp2) | bf (N),  rlhip_fqf_frac_nparams(h, N) = N h + N floats.
+ * rlhip_fqf_frac_init_f32: Wf[q] = ((2 u - 1) sqrtf(6 / (float)(h + N))) * 0.01f (Glorot-uniform x 0.01 as in the paper), bf = 0;
+ * u = u01_f32(word 0 of philox4x32_10(seed, element q, 0, net_id, 15)) -- tag 15 is this stream's own (12..14: NoisyDense).
+ * Envelope: the IQN section's for ns, h, na, n_cos and act; N = n_fractions 2..32 (the N + (N - 1) online rows of a sample fit the 64
+ * level slots per sample); kappa finite and > 0; ent_coef finite and >= 0; anything else is RLHIP_EINVAL before any launch, and
+ * rlhip_fqf_workspace_bytes returns -1.
+ *
+ * All arithmetic is Float32 without contraction; fmaf only where written.  For one state with psi as in the IQN section:
+ *     l[i]     = bf[i], then fmaf(Wf[i, j], psi[j], .) over j ascending                              i = 0 .. N - 1
+ *     mx       = max_i l[i];   z[i] = l[i] - mx;   e[i] = expf(z[i]);   S = sum_i e[i] (ascending);   q[i] = e[i] / S
+ *     lq[i]    = z[i] - logf(S);   H = 0, then fmaf(-q[i], lq[i], .) over i ascending                (the entropy of q)
+ *     tau[0]   = 0;   tau[i + 1] = tau[i] + q[i] (ascending adds) for i + 1 < N;   tau[N] := 1.0f
+ *     that[i]  = 0.5f * (tau[i] + tau[i + 1]);   d[i] = tau[i + 1] - tau[i]
+ *     th(., t) = the IQN section's lines c, phi, m, th at level t.  (e + 1) * t is now a ROUNDED Float32 product (t is not on IQN's
+ *                2^-17 grid), and cospif is taken of that rounded product
+ *     Q[o]     = 0, then fmaf(d[i], th(., that[i])[o], .) over i ascending
+ *
+ * rlhip_fqf_forward_f32 -- n observations (obs SoA, ns x n): q_out SoA (na x n); nullable quantiles_out SoA ((N * na) x n), row
+ * i + N * o = th(., that[i])[o]; nullable tau_out SoA ((N + 1) x n) and tau_hat_out SoA (N x n).  n = 0 is a no-op.
+ * rlhip_fqf_plan_f32 -- plan! in one launch: q_out (nullable) is byte for byte rlhip_fqf_forward_f32 (the same kernel), `actions`
+ * byte for byte rlhip_eps_greedy_select_f32 (no mask, no tie-break) on those values with the same (eps, seed, env_id_base, step).
+ *
+ * rlhip_fqf_grad_batch_f32 -- Algorithm 1 of the paper on a GATHERED batch: the arrays of rlhip_iqn_grad_batch_f32 plus frac_params,
+ * ent_coef, frac_grad_out and the fraction outputs; no seed, no draw counter.  Per sample i:
+ *     tau, that, d, H   of the ONLINE fraction net on psi(s_i) of the online net; used for s_i AND s'_i
+ *                       -> tau_out ((N + 1) x batch SoA), tau_hat_out (N x batch SoA), ent_out (batch)
+ *     a*    = first argmax_o (strict >) of  0, then fmaf(d[j], th_t(s', that[j])[o], .) over j;  double_dqn != 0: of the online net's
+ *             th(s', that[j])[o]                                                                     -> sel_out (i32[batch])
+ *     T_j   = fmaf(c, th_t(s', that[j])[a*], r[i])                                                   -> target_out (N x batch SoA)
+ *     u, hub, dhub, w, rho_n, d_n, L_i, g_n, loss_out   the IQN section's lines with tau_n = that[n] and N' = N   -> ql_out (batch)
+ * Back-propagation through the quantile network is the IQN section's, rows in the same order; the levels, T, a* and the target net are
+ * constants.  Fraction gradient (no gradient into psi or the quantile network), with th_a(t) = th(s_i, t)[a_i] evaluated forward-only
+ * at the N - 1 interior levels tau[1 .. N - 1]:
+ *     gf[k]  = (2.0f * th_a(tau[k]) - th_a(that[k])) - th_a(that[k - 1])                             k = 1 .. N - 1
+ *     dq[N - 1] = 0;  dq[k] = gf[N - 1] + gf[N - 2] + .. + gf[k + 1]  (a chain from +0, added from the top down)
+ *     dq[k]  = fmaf(ent_coef, lq[k] + 1.0f, dq[k])          (minus ent_coef times dH/dq[k] = -(lq[k] + 1))
+ *     m      = 0, then fmaf(q[k], dq[k], .) over k ascending
+ *     dl[k]  = (q[k] * (dq[k] - m)) * (w_i / (float)batch),   w_i = weights[i], or 1.0f without weights
+ *     dWf[k, j] fmaf(dl[k], psi[j], .) over the workgroup's samples in ascending order, from +0;   dbf[k]  adds of dl[k]
+ *   across workgroups: the nb partial rows in ascending w, adds from +0 (the nb rule of the C51 section with np = rlhip_iqn_nparams +
+ *   rlhip_fqf_frac_nparams, tiles of 8 samples).  An action outside 0 .. na - 1 contributes nothing to either gradient and
+ *   ql_out[i] = 0; its fractions, sel_out and target_out are still written.  No float atomics; two calls give the same bytes.
+ * workspace: at least rlhip_fqf_workspace_bytes(ns, h, na, n_cos, N, batch) bytes; no initialisation.
+ *
+ * One update of rlhip.FQFLearner = draw -> gather -> this gradient -> [rlhip_per_priority_f32 on ql_out] -> rlhip_clip_adam_f32 on the
+ * quantile vector and on the fraction vector (each with its own Adam state and norm) -> target sync of the quantile vector.
+ * Out of scope: NoisyDense, dueling, three-layer and bf16 nets, sharded runs, a fused vec-step, UInt8 frames, kappa = 0. */
+int64_t rlhip_fqf_frac_nparams(int64_t h, int64_t n_fractions);
+int32_t rlhip_fqf_frac_init_f32(float* frac_params, int64_t h, int64_t n_fractions, uint64_t seed, uint32_t net_id, rlhip_stream_t stream);
+int32_t rlhip_fqf_forward_f32(const float* params, const float* frac_params, int64_t ns, int64_t h, int64_t na, int64_t n_cos,
+                              int64_t n_fractions, int32_t act, const float* obs, int64_t n, float* q_out, float* quantiles_out,
+                              float* tau_out, float* tau_hat_out, rlhip_stream_t stream);
+int32_t rlhip_fqf_plan_f32(const float* params, const float* frac_params, int64_t ns, int64_t h, int64_t na, int64_t n_cos,
+                           int64_t n_fractions, int32_t act, const float* obs, int64_t n, double eps, uint64_t seed, uint32_t env_id_base,
+                           uint32_t step, int32_t* actions, float* q_out, rlhip_stream_t stream);
+int64_t rlhip_fqf_workspace_bytes(int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_fractions, int64_t batch);
+int32_t rlhip_fqf_grad_batch_f32(int64_t ns, int64_t h, int64_t na, int64_t n_cos, int64_t n_fractions, int32_t act, float kappa,
+                                 float ent_coef, const float* params, const float* target_params, const float* frac_params, const float* s,
+                                 const int32_t* a, const float* r, const uint8_t* term, const float* s_next, int64_t batch, float gamma,
+                                 const int32_t* n_used, const float* weights, int32_t double_dqn, void* workspace, float* grad_out,
+                                 float* frac_grad_out, float* loss_out, float* ql_out, float* target_out, int32_t* sel_out, float* tau_out,
+                                 float* tau_hat_out, float* ent_out, rlhip_stream_t stream);
 
 /* ------------------------------------------------ NoisyDense networks for the categorical learner -- */
 /* (csrc/noisy.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)

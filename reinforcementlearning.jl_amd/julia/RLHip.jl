@@ -31,7 +31,7 @@ using ChainRulesCore: AbstractZero, NoTangent, unthunk
 
 export HipVecEnv, HipCartPoleEnv, HipPendulumEnv, HipMountainCarEnv, HipAcrobotRK4Env, HipTrajectory, HipApproximator,
     HipTargetNetwork, HipDQNLearner, HipQBasedPolicy, HipPPOPolicy, HipComm, HipEpisodeStats, DevBuf, to_host, to_dev!,
-    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner, HipNoisyApproximator, HipDistDuelingApproximator
+    HipPrioritizedTraces, HipStackFrames, HipNStepBatchSampler, DevValues, HipDuelingApproximator, HipCovGaussianNetwork, DevArray, HipRainbowLearner, HipQRDQNLearner, HipIQNApproximator, HipIQNLearner, HipFQFApproximator, HipFQFLearner, HipNoisyApproximator, HipDistDuelingApproximator
 
 const LIB = get(ENV, "RLHIP_LIB", "librlhip.so")
 
@@ -2371,6 +2371,106 @@ function optimise!(L::HipIQNLearner, s, a, r, term, s_next; batch = L.batchsize,
     L.draw_ctr += 1
     L.n_updates += 1
     optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
+    true
+end
+
+# ------------------------------------------------------------------------- fully parameterised quantile function (FQF) learner
+# The ccalls of csrc/fqf.hip (include/rlhip.h, "fully parameterised quantile function (FQF) distributional DQN learner").  The quantile
+# network is HipIQNApproximator's; the fraction-proposal network Dense(h, N) is a second flat vector [Wf | bf] with an Adam state of its
+# own.  One update is  draw -> gather -> optimise!(L, s, a, r, term, s_next)  [-> the priority write-back of L.ql].  Statically checked
+# only: nothing in this section has been executed.
+
+"the fraction-proposal network of FQF: `params` = [Wf (N x h) | bf (N)], its gradient and Adam state"
+mutable struct HipFQFApproximator
+    hidden::Int; n_fractions::Int
+    params::DevBuf{Float32}; grad::DevBuf{Float32}; m::DevBuf{Float32}; v::DevBuf{Float32}; beta_pow::DevBuf{Float32}; gn::DevBuf{Float32}
+    lr::Float32; beta1::Float32; beta2::Float32; eps::Float32
+end
+function HipFQFApproximator(hidden, n_fractions; lr = 2.5f-6, beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, seed = 0, net_id = 0)
+    nf = ccall((:rlhip_fqf_frac_nparams, LIB), Int64, (Int64, Int64), hidden, n_fractions)
+    nf > 0 || throw(ArgumentError("HipFQFApproximator: positive sizes"))
+    p = DevBuf{Float32}(nf)
+    chk(ccall((:rlhip_fqf_frac_init_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}),
+              p.ptr, hidden, n_fractions, seed, net_id, stream()))
+    HipFQFApproximator(hidden, n_fractions, p, DevBuf{Float32}(nf), DevBuf{Float32}(nf), DevBuf{Float32}(nf),
+                       to_dev!(DevBuf{Float32}(2), Float32[beta1, beta2]), DevBuf{Float32}(1), lr, beta1, beta2, eps)
+end
+
+"FQFLearner(approximator = TargetNetwork(ImplicitQuantileNet), fractions = HipFQFApproximator, n_actions, n_cos, κ, ent_coef): the levels of a
+sample are placed by the fraction network on ψ(s).  ns 2..16, h a multiple of 32 and <= 256, 1..4 actions, n_cos even and 2..64, 2..32
+fractions, κ > 0, ent_coef >= 0"
+mutable struct HipFQFLearner <: AbstractLearner
+    approximator::HipTargetNetwork
+    fractions::HipFQFApproximator
+    n_actions::Int; n_cos::Int; N::Int; κ::Float32; ent_coef::Float32
+    batchsize::Int; γ::Float32; max_grad_norm::Float32; double_dqn::Bool
+    n_updates::Int
+    grad::DevBuf{Float32}; loss::DevBuf{Float32}; ql::DevBuf{Float32}; workspace::DevBuf{UInt8}
+end
+function HipFQFLearner(tn::HipTargetNetwork, fr::HipFQFApproximator; n_actions, n_cos = 64, κ = 1f0, ent_coef = 0f0, batchsize = 32,
+                       γ = 0.99f0, max_grad_norm = 0f0, double_dqn = false)
+    net = tn.network
+    net.layers == 2 && net.dueling === nothing || throw(ArgumentError("HipFQFLearner: the network of HipIQNApproximator"))
+    np = ccall((:rlhip_iqn_nparams, LIB), Int64, (Int64, Int64, Int64, Int64), net.n_in, net.hidden, n_actions, n_cos)
+    net.n_out == n_actions && net.params.n == np && fr.hidden == net.hidden ||
+        throw(ArgumentError("the network is not HipIQNApproximator($(net.n_in), $(net.hidden), $n_actions; n_cos = $n_cos)"))
+    isfinite(κ) && κ > 0 || throw(ArgumentError("HipFQFLearner: κ must be finite and > 0 (κ = 0 is out of scope)"))
+    isfinite(ent_coef) && ent_coef >= 0 || throw(ArgumentError("HipFQFLearner: ent_coef must be finite and >= 0"))
+    ws = ccall((:rlhip_fqf_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64, Int64, Int64), net.n_in, net.hidden, n_actions, n_cos,
+               fr.n_fractions, batchsize)
+    ws >= 0 || throw(ArgumentError("the FQF kernels take obs_dim 2..16, hidden a multiple of 32 and <= 256, 1..4 actions, " *
+                                   "n_cos even and 2..64, 2..32 fractions"))
+    HipFQFLearner(tn, fr, n_actions, n_cos, fr.n_fractions, κ, ent_coef, batchsize, γ, max_grad_norm, double_dqn, 0,
+                  DevBuf{Float32}(net.params.n), DevBuf{Float32}(1), DevBuf{Float32}(batchsize), DevBuf{UInt8}(ws))
+end
+
+"forward(learner, s): `q` (n_actions, n) = the d-weighted sum of the quantiles at the placed levels; `quantiles` ((N * n_actions), n), `τ`
+(N + 1, n) and `τ̂` (N, n) may be `nothing`"
+function forward!(q::DevBuf{Float32}, L::HipFQFLearner, obs::DevBuf{Float32}, n; quantiles = nothing, τ = nothing, τ̂ = nothing)
+    net = L.approximator.network
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_fqf_forward_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, L.fractions.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_cos, L.N, net.act, obs.ptr, n, q.ptr,
+              np(quantiles), np(τ), np(τ̂), stream()))
+    q
+end
+
+"plan! in one launch: byte for byte forward! followed by the EpsilonGreedyExplorer's selection (no tie-break).  `actions` (n) 0-based;
+`q` may be `nothing`"
+function plan!(actions::DevBuf{Int32}, L::HipFQFLearner, obs::DevBuf{Float32}, n, ϵ; seed = UInt64(0), env_id_base = UInt32(0),
+               step = UInt32(0), q = nothing)
+    net = L.approximator.network
+    chk(ccall((:rlhip_fqf_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float64, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.params.ptr, L.fractions.params.ptr, net.n_in, net.hidden, L.n_actions, L.n_cos, L.N, net.act, obs.ptr, n, ϵ, seed,
+              env_id_base, step, actions.ptr, q === nothing ? C_NULL : q.ptr, stream()))
+    actions
+end
+
+"loss, per-sample quantile-Huber loss `L.ql` (unweighted) and both gradients on a gathered batch, then clip + Adam on the quantile vector
+(and the target sync) through optimise!(tn, grad) and clip + Adam on the fraction vector.  `n_used`, `weights`, `target` ((N, batch)),
+`sel` (Int32, batch), `τ`, `τ̂` and `ent` may be `nothing`"
+function optimise!(L::HipFQFLearner, s, a, r, term, s_next; batch = L.batchsize, γ = L.γ, n_used = nothing, weights = nothing,
+                   target = nothing, sel = nothing, τ = nothing, τ̂ = nothing, ent = nothing)
+    tn, net, fr = L.approximator, L.approximator.network, L.fractions
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_fqf_grad_batch_f32, LIB), Int32,
+              (Int64, Int64, Int64, Int64, Int64, Int32, Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              net.n_in, net.hidden, L.n_actions, L.n_cos, L.N, net.act, L.κ, L.ent_coef, net.params.ptr, tn.target.ptr, fr.params.ptr, s.ptr,
+              a.ptr, r.ptr, term.ptr, s_next.ptr, batch, γ, np(n_used), np(weights), Int32(L.double_dqn), L.workspace.ptr, L.grad.ptr,
+              fr.grad.ptr, L.loss.ptr, L.ql.ptr, np(target), np(sel), np(τ), np(τ̂), np(ent), stream()))
+    L.n_updates += 1
+    optimise!(tn, L.grad; clip_norm = L.max_grad_norm)
+    chk(ccall((:rlhip_clip_adam_f32, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Float32, Float32,
+               Ptr{Cvoid}, Ptr{Cvoid}),
+              fr.params.ptr, fr.grad.ptr, fr.m.ptr, fr.v.ptr, fr.beta_pow.ptr, fr.params.n, 1f0, L.max_grad_norm, fr.lr, fr.beta1, fr.beta2,
+              fr.eps, fr.gn.ptr, stream()))
     true
 end
 

@@ -22,6 +22,7 @@ from .sac import SACPolicy  # noqa: F401
 from .c51 import RainbowLearner, c51_forward, c51_grad_batch, c51_plan, c51_workspace  # noqa: F401
 from .qrdqn import QRDQNLearner, qrdqn_forward, qrdqn_grad_batch, qrdqn_plan, qrdqn_workspace  # noqa: F401
 from .iqn import IQNApproximator, IQNLearner, iqn_forward, iqn_grad_batch, iqn_nparams, iqn_plan, iqn_workspace  # noqa: F401
+from .fqf import FQFApproximator, FQFLearner, fqf_forward, fqf_frac_nparams, fqf_grad_batch, fqf_plan, fqf_workspace  # noqa: F401
 from .noisy import NoisyApproximator, noisy_c51_forward, noisy_c51_plan, noisy_init, noisy_nparams, noisy_plan_tile  # noqa: F401
 from .dist_dueling import (DistDuelingApproximator, NoisyDuelingApproximator, dist_dueling_nparams, noisy_c51_dueling_forward,  # noqa: F401
                            noisy_c51_dueling_plan)

@@ -349,6 +349,13 @@ _PROTOS = {
     "rlhip_iqn_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64, i64]),
     "rlhip_iqn_grad_batch_f32": (i32, [i64, i64, i64, i64, i64, i64, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, u64, u32,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rlhip_fqf_frac_nparams": (i64, [i64, i64]),
+    "rlhip_fqf_frac_init_f32": (i32, [vp, i64, i64, u64, u32, vp]),
+    "rlhip_fqf_forward_f32": (i32, [vp, vp, i64, i64, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
+    "rlhip_fqf_plan_f32": (i32, [vp, vp, i64, i64, i64, i64, i64, i32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
+    "rlhip_fqf_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64]),
+    "rlhip_fqf_grad_batch_f32": (i32, [i64, i64, i64, i64, i64, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, i32, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "rlhip_noisy_nparams": (i64, [i64, i64, i64]),
     "rlhip_noisy_plan_tile": (i64, []),
     "rlhip_noisy_init_f32": (i32, [vp, i64, i64, i64, u64, u32, f32, vp]),

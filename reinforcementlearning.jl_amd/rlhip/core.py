@@ -380,6 +380,9 @@ def _refuse_sac(policy, loop):
         if type(policy.learner).__name__ == "IQNLearner":
             raise NotImplementedError(f"{loop}: a fused vec-step for IQNLearner (quantiles at drawn levels, an implicit-quantile "
                                       "network) is out of scope; use the per-stage loop, rlhip.run")
+        if type(policy.learner).__name__ == "FQFLearner":
+            raise NotImplementedError(f"{loop}: a fused vec-step for FQFLearner (quantiles at levels a fraction-proposal network "
+                                      "places) is out of scope; use the per-stage loop, rlhip.run")
         if type(policy.learner).__name__ == "QRDQNLearner":
             raise NotImplementedError(f"{loop}: a fused vec-step for QRDQNLearner (quantiles of the value distribution per action) is "
                                       "out of scope; use the per-stage loop, rlhip.run")

@@ -6,7 +6,8 @@ a drawn level tau to one quantile per action, th = header(psi(s) .* phi(cos.(pi 
 between N online and N' target levels (Dabney et al. 2018).  The Zoo's IQNLearner is not in the reference snapshot, so include/rlhip.h
 states the update (csrc/iqn.hip implements it, tests/iqn_ref.py states the mathematics in Float64).
 
-Out of scope, refused by name: FQF, kappa = 0, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
+FQF (levels placed by a fraction-proposal network) is FQFLearner, rlhip/fqf.py.
+Out of scope, refused by name: kappa = 0, NoisyDense, a fused vec-step, three-layer and bf16 networks, dueling distributional
 heads, sharded runs (world > 1), UInt8 frames.
 """
 import math

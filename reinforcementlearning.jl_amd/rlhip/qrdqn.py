@@ -7,7 +7,8 @@ the shipped two-layer layout with n_actions * n_quantiles output rows, row k + n
 
 Dueling heads: QRDQNLearner over TargetNetwork(DistDuelingApproximator(ns, h, n_actions, n_quantiles)) (rlhip/dist_dueling.py).
 
-Out of scope, refused by name: FQF, kappa = 0, NoisyDense (a NoisyDuelingApproximator too), a fused vec-step, three-layer and bf16
+FQF (levels placed by a fraction-proposal network) is FQFLearner, rlhip/fqf.py.
+Out of scope, refused by name: kappa = 0, NoisyDense (a NoisyDuelingApproximator too), a fused vec-step, three-layer and bf16
 networks, a scalar DuelingApproximator, sharded runs (world > 1), UInt8 frames.
 """
 import math
