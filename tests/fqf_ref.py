@@ -36,7 +36,8 @@ def forward(p, pf, dims, N, act, x, tau=None):
 
 def loss(p, pt, pf, dims, N, act, kappa, ent_coef, s, a, r, term, sn, gamma, n_used=None, weights=None, double=False, tau=None):
     """-> dict(loss: the quantile-Huber loss (differentiate by p), frac_loss: the fraction surrogate (differentiate by pf), ql (B),
-    target (N, B), sel (B), tau, that, ent (B), margin: the smallest a* margin)"""
+    target (N, B), sel (B), tau, that, ent (B), margin: the smallest a* margin, zs: the pre-activations (psi where act is relu, phi
+    always) of every network evaluation in the loss, zmin: the smallest |z| among them)"""
     na, B, dt = dims[2], s.shape[1], p.dtype
     g32 = np.float64(np.float32(gamma))
     disc = torch.full((B,), float(g32), dtype=dt)
@@ -48,14 +49,21 @@ def loss(p, pt, pf, dims, N, act, kappa, ent_coef, s, a, r, term, sn, gamma, n_u
     that, d = mids(tau)
     cols = torch.arange(B)
     with torch.no_grad():
-        tht = net(pt, dims, act, sn, that)[0]
-        qsel = (d[:, None, :] * (net(p, dims, act, sn, that)[0] if double else tht)).sum(0)
+        tht, zp_t, zf_t = net(pt, dims, act, sn, that)
+        zs = [zf_t] + ([zp_t] if act == 0 else [])
+        tho = tht
+        if double:
+            tho, zp_o, zf_o = net(p, dims, act, sn, that)
+            zs += [zf_o] + ([zp_o] if act == 0 else [])
+        qsel = (d[:, None, :] * tho).sum(0)
         sel = qsel.argmax(0)
         top = qsel.topk(2, 0).values if na > 1 else None
         T = r[None] + c[None] * tht[:, sel, cols]
     valid = (a >= 0) & (a < na)
     ac = a.clamp(0, na - 1).long()
-    th = net(p, dims, act, s, that)[0][:, ac, cols]
+    th, zp, zf = net(p, dims, act, s, that)
+    zs += [zf.detach()] + ([zp.detach()] if act == 0 else [])
+    th = th[:, ac, cols]
     u = T[None, :, :] - th[:, None, :]
     hub = torch.where(u.abs() <= kappa, 0.5 * u * u, kappa * (u.abs() - 0.5 * kappa)) / kappa
     w = torch.where(u < 0, 1.0 - that[:, None, :], that[:, None, :])
@@ -63,7 +71,10 @@ def loss(p, pt, pf, dims, N, act, kappa, ent_coef, s, a, r, term, sn, gamma, n_u
     wts = (weights if weights is not None else torch.ones(B, dtype=dt)) * valid.to(dt)
     # the paper's fraction gradient as a surrogate: d/dtau_i of the 1-Wasserstein distance is gf[i], i = 1 .. N - 1
     with torch.no_grad():
-        gf = 2.0 * net(p, dims, act, s, tau[1:-1])[0][:, ac, cols] - th[1:] - th[:-1]
+        thi, _, zf_i = net(p, dims, act, s, tau[1:-1])  # (psi(s) is in zs already)
+        zs.append(zf_i)
+        gf = 2.0 * thi[:, ac, cols] - th[1:] - th[:-1]
     frac = (wts * ((gf * tau_own[1:-1]).sum(0) - ent_coef * H)).sum() / B
     return dict(loss=(ql * wts).sum() / B, frac_loss=frac, ql=ql.detach(), target=T, sel=sel.to(torch.int32), tau=tau, that=that,
-                ent=H.detach(), margin=float((top[0] - top[1]).min()) if top is not None else np.inf)
+                ent=H.detach(), margin=float((top[0] - top[1]).min()) if top is not None else np.inf, zs=zs,
+                zmin=min(float(z.abs().min()) for z in zs))
