@@ -1459,6 +1459,79 @@ int32_t rlhip_sac_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
                                  float* alpha_out, void* workspace, float* grad_out, float* stats_out, int32_t* sel_out,
                                  float* logp_out, rlhip_stream_t stream);
 
+/* ------------------------------------------------------------------------ TD3 and DDPG -- */
+/* (csrc/td3.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The reference's homepage lists DDPG among its algorithms and its docs build MADDPG on DDPGPolicy, but the Zoo's DDPGPolicy and
+ * TD3Policy are not in the reference snapshot: parity with them is unpinned, and THIS TEXT is the specification (tests/td3_ref.py is
+ * its Float64 model).  DDPG is n_critics = 1 with target_noise = 0 (and policy_freq = 1 on the host).
+ *
+ * Scope: record rings (Float32 observations, obs_dim = ns in 2..4), ONE action component, two-layer Float32 networks with h a
+ * multiple of 16 in 16..256, act 0 relu / 1 tanh, n_critics 1 or 2.  A frame ring, another obs_dim, h, act or n_critics, batch < 1,
+ * an empty ring or a NULL array that is not nullable is RLHIP_EINVAL before any launch.  All arithmetic is Float32 without
+ * contraction; fmaf only where written.  clampj(x, lo, hi) = x > hi ? hi : (x < lo ? lo : x) (csrc/head_device.h).
+ *
+ * Networks, flat as rlhip_mlp2_nparams / rlhip_mlp2_init_f32 lay them out:
+ *     actor          = mlp2(ns, h, 1): the action is action_scale * tanhf(mu(s))
+ *     critics        = [Q1 | Q2] ([Q1] with n_critics = 1), each mlp2(ns + 1, h, 1) on vcat(s, u): input row ns is the action
+ *     actor_target, critic_targets = copies              (init net_ids: 0 actor, 1 and 2 the critics)
+ *
+ * rlhip_td3_plan_f32 -- plan! for n envs in one launch, one lane per env.  obs SoA (ns x n).  mu is the ONE chain of
+ * rlhip_mlp2_forward_f32 (mu = b2, fmaf(W2[j], act(z[j]), .) over j ascending), and mu_out (nullable, n) is byte for byte its output.
+ *     action_out[i] = clampj(action_scale * tanhf(mu) + act_noise * normal_draw(seed, env_id_base + i, step, 0), action_lo, action_hi)
+ * deterministic != 0 draws nothing and adds nothing: action_out[i] = clampj(action_scale * tanhf(mu), action_lo, action_hi).  n = 0
+ * is a no-op.
+ *
+ * The unit-sliced forward -- EVERY forward pass inside the two gradient launches (it differs from rlhip_mlp2_forward_f32 in the
+ * order of the layer-2 sum only).  One 16-lane row owns a (sample, network) pair.  Lane p takes the units j = p, p + 16, .. ascending:
+ *     z[j] = b1[j], fmaf(W1[j, k], x[k], .) over k ascending;     part_p = +0, fmaf(W2[j], act(z[j]), part_p) over its units
+ *     the 16 partials by the shift-down tree  v[i] += v[i + 8];  v[i] += v[i + 4];  v[i] += v[i + 2];  v[i] += v[i + 1]  (i = 0 ends
+ *     as ((p0 + p8) + (p4 + p12)) + ((p2 + p10) + (p6 + p14)) + the same of the odd lanes);  out = tree + b2
+ *
+ * rlhip_td3_critic_grad_f32 -- ring, record and idx rules of rlhip_sac_critic_grad_f32.  Per sample i:
+ *     e    = target_noise == 0 ? +0 (no draw) : clampj(target_noise * normal_draw(seed, i, step, 0), -noise_clip, noise_clip)
+ *     u'   = clampj(action_scale * tanhf(mu_t(s')) + e, action_lo, action_hi)          (mu_t: actor_target)
+ *     qt   = Qt2(x') < Qt1(x') ? Qt2(x') : Qt1(x'),  x' = vcat(s', u')                  (Qt1(x') alone with n_critics = 1)
+ *     cont = t ? 0 : 1;    y = r + (gamma * cont) * qt
+ *     x = vcat(s, a);  per critic c:  d_c = Q_c(x) - y;  l_c = d_c * d_c;  g_c = (2.0f * d_c) / (float)batch
+ *     loss_out[c - 1] = (sum_i l_c) / (float)batch                                      (f32[n_critics])
+ *     grad_out = [back-propagation of g_1 through Q1 | of g_2 through Q2]               (y is a constant)
+ *     y_out (nullable) f32[batch];   noise_out (nullable) f32[batch] = e
+ * Back-propagation of g through a network with one output, per sample and hidden unit j (hv = act(z[j]), act' = hv > 0 ? 1 : 0 for
+ * relu, 1 - hv hv for tanh):  dW2[j] = fmaf(g, hv, .);  dz = (g * W2[j]) * act';  db1[j] += dz;  dW1[j, k] = fmaf(dz, x[k], .);  db2 += g.
+ *
+ * rlhip_td3_actor_grad_f32 -- `critics` points at Q1 (the critics the critic update has already stepped).  No draw.  Per sample i:
+ *     a = tanhf(mu(s));  u = action_scale * a;  x = vcat(s, u);  l_i = -Q1(x)
+ *     stats_out = { (sum l_i) / fb, (sum Q1(x)) / fb },  fb = (float)batch;   dq = -1.0f / fb
+ *     du   = per lane p  +0, fmaf((dq * W2[j]) * act'(z[j]), W1[j, ns], .) over its units, then the same tree (the critics get no gradient)
+ *     dmu  = (action_scale * du) * (1.0f - a * a)
+ *     grad_out = back-propagation of dmu through the actor (x = s)
+ *
+ * Summation order of both gradients -- that of the SAC section: tiles of 64 samples, workgroup g of nb = min(tiles, 256) owns tiles
+ * g, g + nb, ..; every gradient element and every loss / statistic sum is ONE fmaf / add chain from +0 over the workgroup's samples in
+ * ascending batch position; the nb partial rows in four groups of ceil(nb / 4), ascending inside a group, ((g0 + g1) + g2) + g3; the
+ * partial loss / statistic sums lane-strided over 64 lanes, then the shift-down tree 32, 16, .., 1; / (float)batch.  No float atomics;
+ * two calls on the same inputs give the same bytes.
+ * workspace: at least rlhip_td3_workspace_bytes(ns, h, n_critics, batch) bytes for either call (-1 for a refused shape).
+ *
+ * Stream separation.  One update = rlhip_ring_sample_indices -> critic gradient -> Adam over the critics; on every policy_freq-th
+ * update -> actor gradient -> Adam over the actor -> rlhip_polyak_f32 over both target vectors (rho = 1 - tau).  plan! draws from the
+ * NORMAL stream under `seed` with step = the vec-step counter and id = the env; the critic launch draws under `seed + 1` with step =
+ * the update counter and id = the batch position, draw index 0; the actor launch draws nothing.  No (seed, id, step, index) is used
+ * twice, so exploration noise and target-smoothing noise are independent. */
+int64_t rlhip_td3_workspace_bytes(int64_t ns, int64_t h, int64_t n_critics, int64_t batch);
+int32_t rlhip_td3_plan_f32(const float* actor, int64_t ns, int64_t h, int32_t act, const float* obs, int64_t n, float action_scale,
+                           float act_noise, float action_lo, float action_hi, int32_t deterministic, uint64_t seed,
+                           uint32_t env_id_base, uint32_t step, float* action_out, float* mu_out, rlhip_stream_t stream);
+int32_t rlhip_td3_critic_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, int32_t n_critics, const float* actor_target,
+                                  const float* critics, const float* critic_targets, int64_t batch, const int64_t* idx, float gamma,
+                                  float action_scale, float target_noise, float noise_clip, float action_lo, float action_hi,
+                                  uint64_t seed, uint32_t step, void* workspace, float* grad_out, float* loss_out, float* y_out,
+                                  float* noise_out, rlhip_stream_t stream);
+int32_t rlhip_td3_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                 int64_t batch, const int64_t* idx, float action_scale, void* workspace, float* grad_out,
+                                 float* stats_out, rlhip_stream_t stream);
+
 /* ------------------------------------------ categorical (C51) distributional DQN learner -- */
 /* (csrc/c51.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
  *

@@ -2138,6 +2138,78 @@ function sac_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspac
     grad
 end
 
+# ------------------------------------------------------------------------------------------------------ TD3 and DDPG
+# The ccalls of csrc/td3.hip (include/rlhip.h, "TD3 and DDPG": the formulas, the unit-sliced summation order, the stream separation).
+# As for SAC there is no Julia run loop: these are the bindings a TD3Policy / DDPGPolicy written against RLCore's stages would call:
+#   rlhip_ring_sample_indices -> td3_critic_grad! -> Adam over the critics; every policy_freq-th update -> td3_actor_grad! -> Adam over
+#   the actor -> rlhip_polyak_f32 over both target vectors.
+# `actor` = mlp2(ns, h, 1), `critics` = [Q1 | Q2] ([Q1] for DDPG), each mlp2(ns + 1, h, 1) on vcat(s, u).
+
+"workspace of td3_critic_grad! / td3_actor_grad! in bytes (-1: a shape they refuse)"
+td3_workspace_bytes(ns, h, n_critics, batch) =
+    ccall((:rlhip_td3_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), ns, h, n_critics, batch)
+
+"plan! of a deterministic actor for n envs in one launch: `action` (n) = clamp(action_scale * tanh(mu) + act_noise * N(0, 1), lo, hi);
+`mu` may be `nothing`.  deterministic = true draws nothing and adds nothing"
+function td3_plan!(action::DevBuf{Float32}, actor::DevBuf{Float32}, ns, h, act, obs::DevBuf{Float32}, n; action_scale = 1f0,
+                   act_noise = 0.1f0, action_lo = -1f0, action_hi = 1f0, deterministic = false, seed = UInt64(0),
+                   env_id_base = UInt32(0), step = UInt32(0), mu = nothing)
+    chk(ccall((:rlhip_td3_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Int32, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              actor.ptr, ns, h, act, obs.ptr, n, action_scale, act_noise, action_lo, action_hi, Int32(deterministic), seed, env_id_base,
+              step, action.ptr, mu === nothing ? C_NULL : mu.ptr, stream()))
+    action
+end
+
+"loss (n_critics) and gradient of the critics against y = r + γ (1 - t) min Qt(s', u'), u' = clamp(action_scale tanh(mu_t(s')) + e, lo, hi),
+e = clamp(target_noise N(0, 1), ±noise_clip), on the transitions `idx` of a record ring; `y` and `noise` (batch) may be `nothing`"
+function td3_critic_grad!(grad::DevBuf{Float32}, loss::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act, n_critics,
+                          actor_target::DevBuf{Float32}, critics::DevBuf{Float32}, critic_targets::DevBuf{Float32}, batch, idx, γ;
+                          action_scale = 1f0, target_noise = 0.2f0, noise_clip = 0.5f0, action_lo = -1f0, action_hi = 1f0,
+                          seed = UInt64(0), step = UInt32(0), y = nothing, noise = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_td3_critic_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32, Float32, Float32, Float32,
+               Float32, Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, n_critics, actor_target.ptr, critics.ptr, critic_targets.ptr, batch, idx.ptr, γ, action_scale, target_noise,
+              noise_clip, action_lo, action_hi, seed, step, workspace.ptr, grad.ptr, loss.ptr, np(y), np(noise), stream()))
+    grad
+end
+
+"gradient of the actor loss mean(-Q1(s, action_scale tanh(mu(s)))) against the critics the critic step has already moved (`critics`
+starts with Q1) and its statistics `stats` (loss, mean Q1)"
+function td3_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                         actor::DevBuf{Float32}, critics::DevBuf{Float32}, batch, idx; action_scale = 1f0)
+    chk(ccall((:rlhip_td3_actor_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, batch, idx.ptr, action_scale, workspace.ptr, grad.ptr, stats.ptr, stream()))
+    grad
+end
+
+"TD3Policy (n_critics = 2) / DDPGPolicy (n_critics = 1, target_noise = 0, policy_freq = 1): the networks, their targets and the scalars of
+the update.  `td3_critic_step!` opens an update; the optimiser and Polyak steps are the caller's"
+mutable struct HipTD3Policy <: AbstractPolicy
+    actor::DevBuf{Float32}; actor_target::DevBuf{Float32}; critics::DevBuf{Float32}; critic_targets::DevBuf{Float32}
+    ns::Int; hidden::Int; act::Int32; n_critics::Int32
+    γ::Float32; action_scale::Float32; action_lo::Float32; action_hi::Float32
+    act_noise::Float32; target_noise::Float32; noise_clip::Float32; policy_freq::Int
+    seed::UInt64; n_updates::Int
+    actor_grad::DevBuf{Float32}; critic_grad::DevBuf{Float32}; critic_loss::DevBuf{Float32}; actor_stats::DevBuf{Float32}
+    workspace::DevBuf{UInt8}
+end
+
+"the critic gradient of update `p.n_updates` on `idx` -> whether this update also steps the actor (every policy_freq-th): the caller
+steps the critics with its optimiser first, then calls `td3_actor_grad!` against them, steps the actor and moves both targets"
+function td3_critic_step!(p::HipTD3Policy, t::HipTrajectory, batch, idx)
+    td3_critic_grad!(p.critic_grad, p.critic_loss, p.workspace, t, p.hidden, p.act, p.n_critics, p.actor_target, p.critics,
+                     p.critic_targets, batch, idx, p.γ; action_scale = p.action_scale, target_noise = p.target_noise,
+                     noise_clip = p.noise_clip, action_lo = p.action_lo, action_hi = p.action_hi, seed = p.seed + UInt64(1),
+                     step = UInt32(p.n_updates))
+    p.n_updates += 1
+    p.n_updates % p.policy_freq == 0
+end
+
 # ------------------------------------------------------------------------------- categorical (C51) distributional DQN
 # The ccalls of csrc/c51.hip (include/rlhip.h, "categorical (C51) distributional DQN learner": formulas, roundings, summation order).
 # The network is HipApproximator(n_in, hidden, n_actions * n_atoms): output row k + n_atoms * o is atom k of action o.  The gradient

@@ -19,6 +19,7 @@ from .timing import disable_debug_timings, enable_debug_timings, timer  # noqa: 
 from .heads import CategoricalNetwork, CovGaussianNetwork, GaussianNetwork, SoftGaussianNetwork  # noqa: F401
 from .ppo import PPOPolicy, PPOTrajectory, make_ppo_cfg  # noqa: F401
 from .sac import SACPolicy  # noqa: F401
+from .td3 import DDPGPolicy, TD3Policy  # noqa: F401
 from .c51 import RainbowLearner, c51_forward, c51_grad_batch, c51_plan, c51_workspace  # noqa: F401
 from .qrdqn import QRDQNLearner, qrdqn_forward, qrdqn_grad_batch, qrdqn_plan, qrdqn_workspace  # noqa: F401
 from .iqn import IQNApproximator, IQNLearner, iqn_forward, iqn_grad_batch, iqn_nparams, iqn_plan, iqn_workspace  # noqa: F401
