@@ -1532,6 +1532,74 @@ int32_t rlhip_td3_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t a
                                  int64_t batch, const int64_t* idx, float action_scale, void* workspace, float* grad_out,
                                  float* stats_out, rlhip_stream_t stream);
 
+/* ----------------------------------------------- TD3 and DDPG with two hidden layers -- */
+/* (csrc/td3_mlp3.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
+ *
+ * The update of the section above on three-layer Float32 networks (256-256 in the TD3 paper's code, 400-300 in the DDPG paper); as
+ * there, parity with the Zoo is unpinned and THIS TEXT is the specification (tests/td3_mlp3_ref.py is its Float64 model).  The
+ * formulas of e, u', qt, y, d_c, l_c, g_c, loss_out, the actor loss, stats_out and dmu, the nullable outputs, the argument lists and
+ * the stream separation (`seed` for plan!, `seed + 1` for the critic update, ids and steps) carry over line for line; only "network"
+ * now means three layers, and back-propagation gains the middle layer.  There is no packed copy of any weight.
+ *
+ * Scope: record rings (obs_dim = ns in 2..4), ONE action component, h a multiple of 32 in 32..256, act 0 relu / 1 tanh on BOTH
+ * hidden layers, n_critics 1 or 2, batch >= 1.  Anything else (a frame ring, an empty ring, a NULL array that is not nullable) is
+ * RLHIP_EINVAL before any launch, and -1 from rlhip_td3_mlp3_workspace_bytes.
+ *
+ * Networks, flat as rlhip_mlp3_nparams / rlhip_mlp3_init_f32 lay them out (W1 (h x ni) | b1 | W2 (h x h) | b2 | W3 (1 x h) | b3,
+ * column-major: W2[j, k] at j + h k):
+ *     actor          = mlp3(ns, h, 1);   critics = [Q1 | Q2] ([Q1] with n_critics = 1), each mlp3(ns + 1, h, 1) on vcat(s, u)
+ *     actor_target, critic_targets = copies              (init net_ids: 0 actor, 1 and 2 the critics)
+ *
+ * The forward pass, EVERY one of them.  Samples (envs) are cut into tiles of 32; per sample m:
+ *     z1[j] = b1[j], fmaf(W1[j, k], x[k], .) over k ascending;                a1 = act(z1)
+ *     z2[j] = b2[j], then over k ascending  z2[j] + a1[k] * W2[j, k]  as the k-steps of v_mfma_f32_32x32x2_f32 with b2[j] as the
+ *             accumulator's initial value -- bit for bit the ascending fmaf chain (tools/micro/mfma_f32_l1.hip);  a2 = act(z2)
+ *     out   = gradient launches: per lane p of a 16-lane row  +0, fmaf(W3[j], a2[j], .) over j = p, p + 16, .., the shift-down tree of
+ *             the section above, + b3;      plan!: ONE chain  b3, fmaf(W3[j], a2[j], .) over j ascending
+ *
+ * rlhip_td3_mlp3_plan_f32 -- one launch, a tile of 32 envs per workgroup.  mu_out (nullable, n) is the plan! chain above;
+ *     action_out[i] = clampj(action_scale * tanhf(mu) + act_noise * normal_draw(seed, env_id_base + i, step, 0), action_lo, action_hi)
+ * deterministic != 0 draws nothing and adds nothing.  n = 0 is a no-op.
+ *
+ * rlhip_td3_mlp3_critic_grad_f32 -- THREE launches on the stream, in this order:
+ *     1  target pass (forward only; actor target, Qt1, Qt2): e, u', qt and y of every sample; y -> workspace (and y_out), e -> noise_out
+ *     2  gradient launch on a (tile group, critic) grid: Q_c(x), d_c, l_c, g_c against launch 1's y, back-propagation of g_c
+ *     3  the fold
+ * rlhip_td3_mlp3_actor_grad_f32 -- TWO launches: the gradient launch (actor forward; Q1 forward on vcat(s, action_scale a); the
+ * pull-back of dq = -1.0f / fb through Q1 to the action input, the critics get no gradient; the actor forward again, the same bits;
+ * back-propagation of dmu through the actor), then the fold.
+ *     du  = per lane p of a 16-lane row  +0, fmaf(dz1[j], W1[j, ns], .) over j = p, p + 16, .., the tree      (dz1 of Q1, below, g = dq)
+ *     dmu = (action_scale * du) * (1.0f - a * a)
+ *
+ * Back-propagation of g through a network, per sample m (act'(v) = v > 0 ? 1 : 0 for relu, 1 - v v for tanh, of the ACTIVATION v):
+ *     dW3[j] = fmaf(g, a2[j], .);   db3 += g;   dz2[j] = (g * W3[j]) * act'(a2[j]);   db2[j] += dz2[j]
+ *     dW2[j, k]: the MFMA chain  . + dz2[m][j] * a1[m][k]  with the SAMPLE m as the k dimension
+ *     da1[k] = +0, then over j ascending  . + dz2[j] * W2[j, k]  (an MFMA chain over j);   dz1[k] = da1[k] * act'(a1[k])
+ *     db1[k] += dz1[k];   dW1[k, i] = fmaf(dz1[k], x[i], .)
+ *
+ * Summation order of both gradients -- fixed, a function of (batch, h, ns, n_critics) only; no float atomics; two calls on the same
+ * inputs give the same bytes:
+ *   batch sums  tiles of 32 samples; nb = min(tiles, 256, 16 MiB / (4 np)) workgroups per network, np the length of grad_out;
+ *               workgroup g owns tiles g, g + nb, ..; every gradient element (dW2's MFMA accumulators are carried in registers across
+ *               the tiles) and every loss / statistic sum is ONE chain from +0 over the workgroup's samples in ascending batch
+ *               position.  A position past the batch enters with g = +0
+ *   across workgroups: the fold of the section above (four groups of ceil(nb / 4) partial rows, ((g0 + g1) + g2) + g3; the partial
+ *               sums lane-strided over 64 lanes, the shift-down tree, / (float)batch)
+ * workspace: at least rlhip_td3_mlp3_workspace_bytes(ns, h, n_critics, batch) bytes for either call: the partial rows, the partial
+ * sums and the batch's TD targets; no initialisation. */
+int64_t rlhip_td3_mlp3_workspace_bytes(int64_t ns, int64_t h, int64_t n_critics, int64_t batch);
+int32_t rlhip_td3_mlp3_plan_f32(const float* actor, int64_t ns, int64_t h, int32_t act, const float* obs, int64_t n, float action_scale,
+                                float act_noise, float action_lo, float action_hi, int32_t deterministic, uint64_t seed,
+                                uint32_t env_id_base, uint32_t step, float* action_out, float* mu_out, rlhip_stream_t stream);
+int32_t rlhip_td3_mlp3_critic_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, int32_t n_critics, const float* actor_target,
+                                       const float* critics, const float* critic_targets, int64_t batch, const int64_t* idx,
+                                       float gamma, float action_scale, float target_noise, float noise_clip, float action_lo,
+                                       float action_hi, uint64_t seed, uint32_t step, void* workspace, float* grad_out,
+                                       float* loss_out, float* y_out, float* noise_out, rlhip_stream_t stream);
+int32_t rlhip_td3_mlp3_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                      int64_t batch, const int64_t* idx, float action_scale, void* workspace, float* grad_out,
+                                      float* stats_out, rlhip_stream_t stream);
+
 /* ------------------------------------------ categorical (C51) distributional DQN learner -- */
 /* (csrc/c51.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
  *

@@ -34,6 +34,7 @@ NO_SLP = ["-fno-slp-vectorize", "-fno-vectorize"]  # (the loop vectorizer packs 
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP, "iqn.hip": NO_SLP + NO_PK,
          "fqf.hip": NO_SLP + NO_PK,  # (the same MFMA stages as iqn.hip: csrc/iqn_device.h)
+         "td3_mlp3.hip": NO_SLP + NO_PK,  # (the f32 MFMA of iqn.hip on the hidden x hidden layer, forward and backward)
          "noisy.hip": NO_PK}  # (no MFMA in noisy.hip: the vectorizers stay on, the packed f32 forms are off at the target)
 
 

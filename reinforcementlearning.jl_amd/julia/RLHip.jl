@@ -2187,6 +2187,43 @@ function td3_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspac
     grad
 end
 
+# ---- two hidden layers (csrc/td3_mlp3.hip; include/rlhip.h, "TD3 and DDPG with two hidden layers"): the same argument lists on
+# `actor` = mlp3(ns, h, 1), `critics` = [Q1 | Q2], each mlp3(ns + 1, h, 1), h a multiple of 32 in 32..256 (HipTD3Policy(...; layers = 3))
+td3_mlp3_workspace_bytes(ns, h, n_critics, batch) =
+    ccall((:rlhip_td3_mlp3_workspace_bytes, LIB), Int64, (Int64, Int64, Int64, Int64), ns, h, n_critics, batch)
+
+function td3_mlp3_plan!(action::DevBuf{Float32}, actor::DevBuf{Float32}, ns, h, act, obs::DevBuf{Float32}, n; action_scale = 1f0,
+                        act_noise = 0.1f0, action_lo = -1f0, action_hi = 1f0, deterministic = false, seed = UInt64(0),
+                        env_id_base = UInt32(0), step = UInt32(0), mu = nothing)
+    chk(ccall((:rlhip_td3_mlp3_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Float32, Int32, UInt64, UInt32, UInt32,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              actor.ptr, ns, h, act, obs.ptr, n, action_scale, act_noise, action_lo, action_hi, Int32(deterministic), seed, env_id_base,
+              step, action.ptr, mu === nothing ? C_NULL : mu.ptr, stream()))
+    action
+end
+
+function td3_mlp3_critic_grad!(grad::DevBuf{Float32}, loss::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act, n_critics,
+                               actor_target::DevBuf{Float32}, critics::DevBuf{Float32}, critic_targets::DevBuf{Float32}, batch, idx, γ;
+                               action_scale = 1f0, target_noise = 0.2f0, noise_clip = 0.5f0, action_lo = -1f0, action_hi = 1f0,
+                               seed = UInt64(0), step = UInt32(0), y = nothing, noise = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_td3_mlp3_critic_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32, Float32, Float32, Float32,
+               Float32, Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, n_critics, actor_target.ptr, critics.ptr, critic_targets.ptr, batch, idx.ptr, γ, action_scale, target_noise,
+              noise_clip, action_lo, action_hi, seed, step, workspace.ptr, grad.ptr, loss.ptr, np(y), np(noise), stream()))
+    grad
+end
+
+function td3_mlp3_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                              actor::DevBuf{Float32}, critics::DevBuf{Float32}, batch, idx; action_scale = 1f0)
+    chk(ccall((:rlhip_td3_mlp3_actor_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, batch, idx.ptr, action_scale, workspace.ptr, grad.ptr, stats.ptr, stream()))
+    grad
+end
+
 "TD3Policy (n_critics = 2) / DDPGPolicy (n_critics = 1, target_noise = 0, policy_freq = 1): the networks, their targets and the scalars of
 the update.  `td3_critic_step!` opens an update; the optimiser and Polyak steps are the caller's"
 mutable struct HipTD3Policy <: AbstractPolicy
@@ -2197,12 +2234,15 @@ mutable struct HipTD3Policy <: AbstractPolicy
     seed::UInt64; n_updates::Int
     actor_grad::DevBuf{Float32}; critic_grad::DevBuf{Float32}; critic_loss::DevBuf{Float32}; actor_stats::DevBuf{Float32}
     workspace::DevBuf{UInt8}
+    layers::Int  # 2: mlp2 vectors and csrc/td3.hip; 3: mlp3 vectors (two hidden layers) and csrc/td3_mlp3.hip
 end
+"the fields in order, `layers` as a keyword (2, the default, or 3)"
+HipTD3Policy(fields...; layers = 2) = HipTD3Policy(fields..., layers)
 
 "the critic gradient of update `p.n_updates` on `idx` -> whether this update also steps the actor (every policy_freq-th): the caller
 steps the critics with its optimiser first, then calls `td3_actor_grad!` against them, steps the actor and moves both targets"
 function td3_critic_step!(p::HipTD3Policy, t::HipTrajectory, batch, idx)
-    td3_critic_grad!(p.critic_grad, p.critic_loss, p.workspace, t, p.hidden, p.act, p.n_critics, p.actor_target, p.critics,
+    (p.layers == 3 ? td3_mlp3_critic_grad! : td3_critic_grad!)(p.critic_grad, p.critic_loss, p.workspace, t, p.hidden, p.act, p.n_critics, p.actor_target, p.critics,
                      p.critic_targets, batch, idx, p.γ; action_scale = p.action_scale, target_noise = p.target_noise,
                      noise_clip = p.noise_clip, action_lo = p.action_lo, action_hi = p.action_hi, seed = p.seed + UInt64(1),
                      step = UInt32(p.n_updates))
