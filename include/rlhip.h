@@ -1600,6 +1600,78 @@ int32_t rlhip_td3_mlp3_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int3
                                       int64_t batch, const int64_t* idx, float action_scale, void* workspace, float* grad_out,
                                       float* stats_out, rlhip_stream_t stream);
 
+/* ------------------------------------------------------- SAC with two hidden layers -- */
+/* (csrc/sac_mlp3.hip on the tile passes of csrc/td3_mlp3_device.h.  Entry points added, no layout or signature changed:
+ * RLHIP_ABI_VERSION stays 2.)
+ *
+ * The update of the "Soft Actor-Critic (SAC)" section on three-layer Float32 networks (256-256 in the SAC paper); parity with the Zoo
+ * is unpinned and THIS TEXT is the specification (tests/sac_mlp3_ref.py is its Float64 model).  The per-sample mathematics -- the lines
+ * "Actor head" to "alpha step" of that section: raw, sg, pass, z, a, u, logp; eps', y; d_c, l_c, g_c, loss_out; sel, q, l_i, stats_out,
+ * dlogp, dq, dact, (dmu, dsg), draw, drho, the alpha step -- the nullable outputs, the argument lists and the stream separation carry
+ * over line for line.  Only "network" now means three layers: the chains are those of "TD3 and DDPG with two hidden layers", here
+ * also at two output rows.  There is no packed copy of any weight.
+ *
+ * Scope: record rings (obs_dim = ns in 2..4), ONE action component, h a multiple of 32 in 32..256, act 0 relu / 1 tanh on BOTH hidden
+ * layers, batch >= 1.  Anything else (a frame ring, an empty ring, a NULL array that is not nullable) is RLHIP_EINVAL before any
+ * launch, and -1 from rlhip_sac_mlp3_workspace_bytes.
+ *
+ * Networks, flat as rlhip_mlp3_nparams / rlhip_mlp3_init_f32 lay them out (W1 | b1 | W2 | b2 | W3 (no x h) | b3 (no), column-major):
+ *     actor    = mlp3(ns, h, 2): output row 0 is mu, row 1 is rho (sigma before its softplus); W3[o, j] at o + 2 j
+ *     critics  = [Q1 | Q2], each mlp3(ns + 1, h, 1) on vcat(s, u);   targets = a copy   (init net_ids: 0 actor, 1 and 2 the critics)
+ *
+ * The forward pass: z1, a1, z2, a2 as in "TD3 and DDPG with two hidden layers" (layer 2 the MFMA chain from b2[j]); layer 3 per
+ * output row o:
+ *     gradient launches: per lane p of a 16-lane row (one row per (sample, output))  +0, fmaf(W3[o, j], a2[j], .) over j = p, p + 16,
+ *                        .., the shift-down tree, + b3[o]
+ *     plan!:             ONE chain per (env, output)  b3[o], fmaf(W3[o, j], a2[j], .) over j ascending
+ *
+ * rlhip_sac_mlp3_plan_f32 -- one launch, a tile of 32 envs per workgroup; eps = normal_draw(seed, env_id_base + i, step, 0).  mu_out /
+ * rho_out (nullable) are the plan! chains; raw_sigma_out (nullable) = softplus_nnlib(rho); action_out / action_scale and logp_out are
+ * byte for byte rlhip_gaussian_head_sample_f32(soft = 1) on mu_out and raw_sigma_out.  deterministic != 0: u = action_scale *
+ * tanhf(mu), no draw, logp_out must be NULL (RLHIP_EINVAL otherwise).  n = 0 is a no-op.
+ *
+ * rlhip_sac_mlp3_critic_grad_f32 -- THREE launches on the stream, in this order:
+ *     1  target pass (forward only): the actor at s', the head on eps' = normal_draw(seed, i, step, 0), Qt1 and Qt2 at vcat(s', u'),
+ *        y = r + (gamma * cont) * (qt - alpha * logp') -> workspace (and y_out)
+ *     2  gradient launch on a (tile group, critic, dW2 half) grid: Q_c(x), d_c, l_c, g_c against launch 1's y, back-propagation of g_c
+ *     3  the fold
+ * rlhip_sac_mlp3_actor_grad_f32 -- TWO launches: the gradient launch, then the fold with the alpha step.  Per tile of 32 samples:
+ *     actor forward at s; the head on eps = normal_draw(seed, i, step, 1); x = vcat(s, u)
+ *     for c = 1, 2 (one after the other, in the same LDS tiles): Q_c(x); the pull-back of dq = -1.0f / fb through Q_c to its action
+ *         input for EVERY sample (dz2, da1, dz1 below with g = dq; no parameter gradient: the critics get none);
+ *         du_c = per lane p of a 16-lane row  +0, fmaf(dz1_c[j], W1_c[j, ns], .) over j = p, p + 16, .., the tree
+ *     sel = Q2(x) < Q1(x) ? 2 : 1;   q = Q_sel(x);   du = sel == 2 ? du_2 : du_1           (a select, never a sum)
+ *     dact, (dmu, dsg), draw, drho, l_i, stats_out as in the SAC section
+ *     actor forward again (the same bits); back-propagation of (dmu, drho) through the actor
+ *
+ * Back-propagation through a network with one output: that of "TD3 and DDPG with two hidden layers".  With the actor's two
+ * cotangents (d_0 = dmu, d_1 = drho), per sample m:
+ *     dW3[o, j] = fmaf(d_o, a2[j], .);   db3[o] += d_o;   dz2[j] = fmaf(drho, W3[1, j], fmaf(dmu, W3[0, j], +0)) * act'(a2[j])
+ *     db2, dW2, da1, dz1, db1, dW1 from dz2 as there
+ *
+ * Summation order of both gradients -- fixed, a function of (batch, h, ns) only; no float atomics; two calls on the same inputs give
+ * the same bytes: tiles of 32 samples; nb = min(tiles, 256, 16 MiB / (4 np)) workgroups per partial row, np the length of grad_out;
+ * workgroup g owns tiles g, g + nb, ..; every gradient element (dW2's MFMA accumulators are carried in registers across the tiles)
+ * and every loss / statistic sum is ONE chain from +0 over the workgroup's samples in ascending batch position, a position past the
+ * batch entering with cotangent +0; across workgroups the fold of the SAC section.  (Above h = 128 the dW2 blocks of a partial row
+ * are dealt over two workgroups in the critic launch and over four in the actor launch; no chain changes.)
+ * workspace: at least rlhip_sac_mlp3_workspace_bytes(ns, h, batch) bytes for either call: the partial rows, the partial sums and the
+ * batch's TD targets; no initialisation. */
+int64_t rlhip_sac_mlp3_workspace_bytes(int64_t ns, int64_t h, int64_t batch);
+int32_t rlhip_sac_mlp3_plan_f32(const float* actor, int64_t ns, int64_t h, int32_t act, const float* obs, int64_t n, float min_sigma,
+                                float max_sigma, float action_scale, int32_t deterministic, uint64_t seed, uint32_t env_id_base,
+                                uint32_t step, float* action_out, float* logp_out, float* mu_out, float* rho_out,
+                                float* raw_sigma_out, rlhip_stream_t stream);
+int32_t rlhip_sac_mlp3_critic_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                       const float* targets, int64_t batch, const int64_t* idx, const float* alpha, float gamma,
+                                       float min_sigma, float max_sigma, float action_scale, uint64_t seed, uint32_t step,
+                                       void* workspace, float* grad_out, float* loss_out, float* y_out, rlhip_stream_t stream);
+int32_t rlhip_sac_mlp3_actor_grad_f32(const rlhip_ring* rb_host, int64_t h, int32_t act, const float* actor, const float* critics,
+                                      int64_t batch, const int64_t* idx, const float* alpha, float min_sigma, float max_sigma,
+                                      float action_scale, uint64_t seed, uint32_t step, float alpha_lr, float target_entropy,
+                                      float* alpha_out, void* workspace, float* grad_out, float* stats_out, int32_t* sel_out,
+                                      float* logp_out, rlhip_stream_t stream);
+
 /* ------------------------------------------ categorical (C51) distributional DQN learner -- */
 /* (csrc/c51.hip.  Entry points added, no layout or signature changed: RLHIP_ABI_VERSION stays 2.)
  *

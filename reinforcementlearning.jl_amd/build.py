@@ -35,6 +35,7 @@ NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA = {"ppo3.hip": NO_SLP, "dqn3.hip": NO_SLP, "ppo3w.hip": NO_SLP, "ppo_grad.hip": NO_SLP, "iqn.hip": NO_SLP + NO_PK,
          "fqf.hip": NO_SLP + NO_PK,  # (the same MFMA stages as iqn.hip: csrc/iqn_device.h)
          "td3_mlp3.hip": NO_SLP + NO_PK,  # (the f32 MFMA of iqn.hip on the hidden x hidden layer, forward and backward)
+         "sac_mlp3.hip": NO_SLP + NO_PK,  # (the same tile passes at two actor outputs: csrc/td3_mlp3_device.h)
          "noisy.hip": NO_PK}  # (no MFMA in noisy.hip: the vectorizers stay on, the packed f32 forms are off at the target)
 
 

@@ -2138,6 +2138,51 @@ function sac_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspac
     grad
 end
 
+# ---- two hidden layers (csrc/sac_mlp3.hip; include/rlhip.h, "SAC with two hidden layers"): the same argument lists on
+# `actor` = mlp3(ns, h, 2), `critics` = [Q1 | Q2], each mlp3(ns + 1, h, 1), h a multiple of 32 in 32..256.  There is no Julia SAC policy
+# type to carry a `layers` field: `sac_grads(layers)` below hands out the four functions of a depth, `layers = 2` (the default) the ones above
+sac_mlp3_workspace_bytes(ns, h, batch) = ccall((:rlhip_sac_mlp3_workspace_bytes, LIB), Int64, (Int64, Int64, Int64), ns, h, batch)
+
+function sac_mlp3_plan!(action::DevBuf{Float32}, actor::DevBuf{Float32}, ns, h, act, obs::DevBuf{Float32}, n; min_sigma = 0f0,
+                        max_sigma = Inf32, action_scale = 1f0, deterministic = false, seed = UInt64(0), env_id_base = UInt32(0),
+                        step = UInt32(0), logp = nothing, mu = nothing, rho = nothing, raw_sigma = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_sac_mlp3_plan_f32, LIB), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Float32, Float32, Float32, Int32, UInt64, UInt32, UInt32, Ptr{Cvoid},
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              actor.ptr, ns, h, act, obs.ptr, n, min_sigma, max_sigma, action_scale, Int32(deterministic), seed, env_id_base, step,
+              action.ptr, np(logp), np(mu), np(rho), np(raw_sigma), stream()))
+    action
+end
+
+function sac_mlp3_critic_grad!(grad::DevBuf{Float32}, loss::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                               actor::DevBuf{Float32}, critics::DevBuf{Float32}, targets::DevBuf{Float32}, batch, idx, alpha::DevBuf{Float32}, γ;
+                               min_sigma = 0f0, max_sigma = Inf32, action_scale = 1f0, seed = UInt64(0), step = UInt32(0), y = nothing)
+    chk(ccall((:rlhip_sac_mlp3_critic_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Float32,
+               Float32, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, targets.ptr, batch, idx.ptr, alpha.ptr, γ, min_sigma, max_sigma, action_scale, seed,
+              step, workspace.ptr, grad.ptr, loss.ptr, y === nothing ? C_NULL : y.ptr, stream()))
+    grad
+end
+
+function sac_mlp3_actor_grad!(grad::DevBuf{Float32}, stats::DevBuf{Float32}, workspace::DevBuf{UInt8}, t::HipTrajectory, h, act,
+                              actor::DevBuf{Float32}, critics::DevBuf{Float32}, batch, idx, alpha::DevBuf{Float32}; min_sigma = 0f0,
+                              max_sigma = Inf32, action_scale = 1f0, seed = UInt64(0), step = UInt32(0), alpha_lr = 0f0,
+                              target_entropy = -1f0, alpha_out = nothing, sel = nothing, logp = nothing)
+    np(x) = x === nothing ? C_NULL : x.ptr
+    chk(ccall((:rlhip_sac_mlp3_actor_grad_f32, LIB), Int32,
+              (Ref{Ring}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Float32, UInt64, UInt32,
+               Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              t.rb, h, act, actor.ptr, critics.ptr, batch, idx.ptr, alpha.ptr, min_sigma, max_sigma, action_scale, seed, step, alpha_lr,
+              target_entropy, np(alpha_out), workspace.ptr, grad.ptr, stats.ptr, np(sel), np(logp), stream()))
+    grad
+end
+
+"the SAC entry points by network depth: `sac_grads(layers)` -> (workspace_bytes, plan!, critic_grad!, actor_grad!)"
+sac_grads(layers = 2) = layers == 3 ? (sac_mlp3_workspace_bytes, sac_mlp3_plan!, sac_mlp3_critic_grad!, sac_mlp3_actor_grad!) :
+                                      (sac_workspace_bytes, sac_plan!, sac_critic_grad!, sac_actor_grad!)
+
 # ------------------------------------------------------------------------------------------------------ TD3 and DDPG
 # The ccalls of csrc/td3.hip (include/rlhip.h, "TD3 and DDPG": the formulas, the unit-sliced summation order, the stream separation).
 # As for SAC there is no Julia run loop: these are the bindings a TD3Policy / DDPGPolicy written against RLCore's stages would call:

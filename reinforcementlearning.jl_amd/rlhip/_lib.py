@@ -342,6 +342,11 @@ _PROTOS = {
     "rlhip_td3_mlp3_critic_grad_f32": (i32, [P(Ring), i64, i32, i32, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, f32, u64, u32, vp, vp,
                                              vp, vp, vp, vp]),
     "rlhip_td3_mlp3_actor_grad_f32": (i32, [P(Ring), i64, i32, vp, vp, i64, vp, f32, vp, vp, vp, vp]),
+    "rlhip_sac_mlp3_workspace_bytes": (i64, [i64, i64, i64]),
+    "rlhip_sac_mlp3_plan_f32": (i32, [vp, i64, i64, i32, vp, i64, f32, f32, f32, i32, u64, u32, u32, vp, vp, vp, vp, vp, vp]),
+    "rlhip_sac_mlp3_critic_grad_f32": (i32, [P(Ring), i64, i32, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, u64, u32, vp, vp, vp, vp, vp]),
+    "rlhip_sac_mlp3_actor_grad_f32": (i32, [P(Ring), i64, i32, vp, vp, i64, vp, vp, f32, f32, f32, u64, u32, f32, f32, vp, vp, vp, vp, vp,
+                                            vp, vp]),
     "rlhip_c51_forward_f32": (i32, [vp, i64, i64, i64, i64, i32, f32, f32, vp, i64, vp, vp, vp, vp]),
     "rlhip_c51_plan_f32": (i32, [vp, i64, i64, i64, i64, i32, f32, f32, vp, i64, f64, u64, u32, u32, vp, vp, vp]),
     "rlhip_c51_workspace_bytes": (i64, [i64, i64, i64, i64, i64]),

@@ -2,11 +2,13 @@
 
 The reference's SoftGaussianNetwork is "mainly used for SAC" (RLCore/src/utils/networks.jl:127-128) and its docs name SACPolicy on
 Pendulum as the continuous off-policy baseline; the type itself left the tree with the Zoo, so include/rlhip.h states the update
-(csrc/sac.hip implements it, tests/sac_ref.py replays it).  The policy fits the unchanged `run(Agent(policy, trajectory), env)`:
+(csrc/sac.hip implements it, tests/sac_ref.py replays it).  `layers = 3` (two hidden layers: 256-256 in the SAC paper) routes the same
+update to csrc/sac_mlp3.hip (the hidden x hidden layer on the f32 MFMA; tests/sac_mlp3_ref.py); `layers = 2`, the default, is the
+path above.  The policy fits the unchanged `run(Agent(policy, trajectory), env)`:
 `Agent` pushes the env's Float32 action tensor through the ring push, so its bits land in the record's action word.
 
 Out of scope, refused by name: more than one action component, frame rings and obs_dim > 4, prioritized or n-step replay,
-importance-sampling weights, three-layer or bf16 networks, a fused vec-step, sharded runs (world > 1), Float64 envs.
+importance-sampling weights, bf16 networks, a fused vec-step, sharded runs (world > 1), Float64 envs.
 """
 import ctypes as C
 import math
@@ -19,11 +21,16 @@ from .ops import ptr, stream_ptr
 
 
 # ----------------------------------------------------------------------------- functional layer
-def sac_workspace(ns, h, batch, device="cuda"):
-    nbytes = int(_lib.lib.rlhip_sac_workspace_bytes(ns, h, batch))
+_ENTRY = {2: "rlhip_sac_", 3: "rlhip_sac_mlp3_"}  # layers -> the prefix of its four entry points
+_HIDDEN = {2: (4, 4), 3: (32, 32)}                # layers -> hidden is a multiple of [0], from [1] up to 256
+
+
+def sac_workspace(ns, h, batch, device="cuda", layers=2):
+    nbytes = int(getattr(_lib.lib, _ENTRY[layers] + "workspace_bytes")(ns, h, batch))
     if nbytes < 0:
-        raise ValueError(f"the SAC kernels take obs_dim 2..4, hidden a multiple of 4 and <= 256, batch >= 1; got obs_dim = {ns}, "
-                         f"hidden = {h}, batch = {batch}")
+        m, lo = _HIDDEN[layers]
+        raise ValueError(f"the SAC kernels (layers = {layers}) take obs_dim 2..4, hidden a multiple of {m} in {lo}..256, batch >= 1; got "
+                         f"obs_dim = {ns}, hidden = {h}, batch = {batch}")
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
@@ -32,36 +39,36 @@ def _opt(t):
 
 
 def sac_plan(actor, ns, h, act, obs, min_sigma, max_sigma, action_scale, seed, env_id_base, step, deterministic=False, action=None,
-             logp=None, mu=None, rho=None, raw_sigma=None):
+             logp=None, mu=None, rho=None, raw_sigma=None, layers=2):
     """plan! for the (ns, n) observations `obs` in one launch -> action (n,); the other outputs are written where given"""
     n = obs.shape[1]
     action = action if action is not None else torch.empty(n, dtype=torch.float32, device=obs.device)
-    call("rlhip_sac_plan_f32", ptr(actor), ns, h, act, ptr(obs), n, min_sigma, max_sigma, action_scale, int(bool(deterministic)), seed,
+    call(_ENTRY[layers] + "plan_f32", ptr(actor), ns, h, act, ptr(obs), n, min_sigma, max_sigma, action_scale, int(bool(deterministic)), seed,
          env_id_base, step, ptr(action), _opt(logp), _opt(mu), _opt(rho), _opt(raw_sigma), stream_ptr())
     return action
 
 
 def sac_critic_grad(traces, h, act, actor, critics, targets, idx, alpha, gamma, min_sigma, max_sigma, action_scale, seed, step,
-                    workspace=None, grad=None, loss=None, y=None):
+                    workspace=None, grad=None, loss=None, y=None, layers=2):
     """loss (2,) and gradient of [Q1 | Q2] against the soft TD target on the transitions `idx` of a record ring -> (grad, loss)"""
     b, dev = idx.numel(), critics.device
-    workspace = workspace if workspace is not None else sac_workspace(traces.obs_dim, h, b, dev)
+    workspace = workspace if workspace is not None else sac_workspace(traces.obs_dim, h, b, dev, layers)
     grad = grad if grad is not None else torch.empty_like(critics)
     loss = loss if loss is not None else torch.empty(2, dtype=torch.float32, device=dev)
-    call("rlhip_sac_critic_grad_f32", C.byref(traces.rb), h, act, ptr(actor), ptr(critics), ptr(targets), b, ptr(idx), ptr(alpha), gamma,
+    call(_ENTRY[layers] + "critic_grad_f32", C.byref(traces.rb), h, act, ptr(actor), ptr(critics), ptr(targets), b, ptr(idx), ptr(alpha), gamma,
          min_sigma, max_sigma, action_scale, seed, step, ptr(workspace), ptr(grad), ptr(loss), _opt(y), stream_ptr())
     return grad, loss
 
 
 def sac_actor_grad(traces, h, act, actor, critics, idx, alpha, min_sigma, max_sigma, action_scale, seed, step, alpha_lr=0.0,
-                   target_entropy=0.0, alpha_out=None, workspace=None, grad=None, stats=None, sel=None, logp=None):
+                   target_entropy=0.0, alpha_out=None, workspace=None, grad=None, stats=None, sel=None, logp=None, layers=2):
     """gradient of the actor loss mean(alpha logp - min(Q1, Q2)) and its statistics (loss, mean q, mean logp) -> (grad, stats); with
     alpha_lr > 0 and `alpha_out` (which may be `alpha`) also the entropy coefficient's step"""
     b, dev = idx.numel(), actor.device
-    workspace = workspace if workspace is not None else sac_workspace(traces.obs_dim, h, b, dev)
+    workspace = workspace if workspace is not None else sac_workspace(traces.obs_dim, h, b, dev, layers)
     grad = grad if grad is not None else torch.empty_like(actor)
     stats = stats if stats is not None else torch.empty(3, dtype=torch.float32, device=dev)
-    call("rlhip_sac_actor_grad_f32", C.byref(traces.rb), h, act, ptr(actor), ptr(critics), b, ptr(idx), ptr(alpha), min_sigma, max_sigma,
+    call(_ENTRY[layers] + "actor_grad_f32", C.byref(traces.rb), h, act, ptr(actor), ptr(critics), b, ptr(idx), ptr(alpha), min_sigma, max_sigma,
          action_scale, seed, step, alpha_lr, target_entropy, _opt(alpha_out), ptr(workspace), ptr(grad), ptr(stats), _opt(sel),
          _opt(logp), stream_ptr())
     return grad, stats
@@ -92,13 +99,14 @@ class SACPolicy:
     update_freq, automatic_entropy_tuning, lr_alpha, target_entropy, ...) on a HipVecEnv with one Float32 action component.
 
     `actor` is mlp2(ns, h, 2) (row 0 mu, row 1 the pre-softplus sigma), `critics` = [Q1 | Q2], each mlp2(ns + 1, h, 1) on
-    vcat(s, u), `targets` their Polyak copy.  One update: draw -> critic gradient -> Adam over [Q1 | Q2] -> actor gradient (against the
+    vcat(s, u), `targets` their Polyak copy; with `layers = 3` every network is mlp3 (two hidden layers of `hidden` units).  One update: draw -> critic gradient -> Adam over [Q1 | Q2] -> actor gradient (against the
     stepped critics) with the alpha step -> Adam over the actor -> Polyak with rho = 1 - tau.  plan! draws under `seed` at the vec-step
     counter, updates under `seed + 1` at the update counter (include/rlhip.h: stream separation)."""
 
     def __init__(self, env, hidden=64, act="relu", gamma=0.99, tau=0.005, alpha=0.2, batchsize=64, start_steps=0, update_after=1000,
                  update_freq=1, automatic_entropy_tuning=True, lr_alpha=3e-3, target_entropy=-1.0, lr=3e-3, min_sigma=0.0,
-                 max_sigma=math.inf, action_scale=None, max_grad_norm=0.0, seed=0, process_group=None):
+                 max_sigma=math.inf, action_scale=None, max_grad_norm=0.0, seed=0, process_group=None, layers=2):
+        from .dqn import mlp3_init
         from .ops import mlp2_init
 
         if not getattr(env, "continuous", False):
@@ -114,9 +122,14 @@ class SACPolicy:
                                       "obs_dim > 4) is out of scope")
         if isinstance(act, str) and act not in ("relu", "tanh"):
             raise ValueError("act must be 'relu' or 'tanh'")
-        if hidden % 4 != 0 or not 4 <= hidden <= 256:
+        if layers not in (2, 3):
+            raise ValueError("layers must be 2 (one hidden layer) or 3 (two hidden layers)")
+        if layers == 2 and (hidden % 4 != 0 or not 4 <= hidden <= 256):
             raise NotImplementedError("SACPolicy: two-layer Float32 networks with hidden a multiple of 4 and <= 256 (three-layer and "
-                                      "bf16 networks are out of scope)")
+                                      "bf16 networks: three-layer ones are layers = 3, bf16 ones are out of scope)")
+        if layers == 3 and (hidden % 32 != 0 or not 32 <= hidden <= 256):
+            raise NotImplementedError("SACPolicy: three-layer Float32 networks (layers = 3) with hidden a multiple of 32 in 32..256 (bf16 "
+                                      "networks are out of scope)")
         if process_group is not None:
             import torch.distributed as dist
 
@@ -125,7 +138,8 @@ class SACPolicy:
         if int(update_freq) < 1 or int(batchsize) < 1:
             raise ValueError("update_freq and batchsize must be >= 1")
         dev = env.device
-        self.n_in, self.hidden = ns, int(hidden)
+        self.n_in, self.hidden, self.layers = ns, int(hidden), int(layers)
+        init = mlp2_init if layers == 2 else mlp3_init
         self.act = {"relu": 0, "tanh": 1}[act] if isinstance(act, str) else int(act)
         self.gamma, self.tau, self.batchsize = float(gamma), float(tau), int(batchsize)
         self.start_steps, self.update_after, self.update_freq = int(start_steps), int(update_after), int(update_freq)
@@ -134,8 +148,8 @@ class SACPolicy:
         self.action_lo, self.action_hi = float(sp.lo[0]), float(sp.hi[0])
         self.action_scale = float(sp.hi[0]) if action_scale is None else float(action_scale)
         self.max_grad_norm, self.seed = float(max_grad_norm), int(seed)
-        self.actor = mlp2_init(ns, self.hidden, 2, self.seed, 0, dev)
-        self.critics = torch.cat([mlp2_init(ns + 1, self.hidden, 1, self.seed, 1, dev), mlp2_init(ns + 1, self.hidden, 1, self.seed, 2, dev)])
+        self.actor = init(ns, self.hidden, 2, self.seed, 0, dev)
+        self.critics = torch.cat([init(ns + 1, self.hidden, 1, self.seed, 1, dev), init(ns + 1, self.hidden, 1, self.seed, 2, dev)])
         self.targets = self.critics.clone()
         self.alpha = torch.tensor([float(alpha)], dtype=torch.float32, device=dev)
         self.actor_opt, self.critic_opt = _Adam(self.actor, lr), _Adam(self.critics, lr)
@@ -145,7 +159,7 @@ class SACPolicy:
         self.actor_grad, self.critic_grad = torch.zeros_like(self.actor), torch.zeros_like(self.critics)
         self.critic_loss = torch.zeros(2, dtype=torch.float32, device=dev)
         self.actor_stats = torch.zeros(3, dtype=torch.float32, device=dev)
-        self.workspace = _Scratch(sac_workspace(ns, self.hidden, self.batchsize, dev))
+        self.workspace = _Scratch(sac_workspace(ns, self.hidden, self.batchsize, dev, self.layers))
         self.last_idx = _Scratch(None)  # the indices of the last update
 
     # ------------------------------------------------------------------------------------ plan!
@@ -154,7 +168,7 @@ class SACPolicy:
         RandomPolicy); `deterministic = True` (evaluation) is action_scale * tanh(mu) and advances no counter."""
         if deterministic:
             return sac_plan(self.actor, self.n_in, self.hidden, self.act, env.state(), self.min_sigma, self.max_sigma, self.action_scale,
-                            self.seed, env.env_id_base, 0, deterministic=True)
+                            self.seed, env.env_id_base, 0, deterministic=True, layers=self.layers)
         self.plan_steps += 1
         step = self.plan_steps
         if step <= self.start_steps:
@@ -163,7 +177,7 @@ class SACPolicy:
             u = fill_uniform(env.n, self.seed, step, 7, env.device)
             return u * (self.action_hi - self.action_lo) + self.action_lo
         return sac_plan(self.actor, self.n_in, self.hidden, self.act, env.state(), self.min_sigma, self.max_sigma, self.action_scale,
-                        self.seed, env.env_id_base, step)
+                        self.seed, env.env_id_base, step, layers=self.layers)
 
     # -------------------------------------------------------------------------------- optimise!
     def check_traces(self, traces):
@@ -200,14 +214,14 @@ class SACPolicy:
         idx = self.last_idx.t = traces.sample_indices(self.batchsize, useed, step) if idx is None else idx
         ws = self.workspace.t
         if idx.numel() != self.batchsize:
-            ws = sac_workspace(self.n_in, h, idx.numel(), self.actor.device)
+            ws = sac_workspace(self.n_in, h, idx.numel(), self.actor.device, self.layers)
         sac_critic_grad(traces, h, self.act, self.actor, self.critics, self.targets, idx, self.alpha, self.gamma, self.min_sigma,
-                        self.max_sigma, self.action_scale, useed, step, ws, self.critic_grad, self.critic_loss)
+                        self.max_sigma, self.action_scale, useed, step, ws, self.critic_grad, self.critic_loss, layers=self.layers)
         self.critic_opt.step_(self.critics, self.critic_grad, self.max_grad_norm)
         tune = self.automatic_entropy_tuning and self.lr_alpha > 0.0
         sac_actor_grad(traces, h, self.act, self.actor, self.critics, idx, self.alpha, self.min_sigma, self.max_sigma,
                        self.action_scale, useed, step, self.lr_alpha if tune else 0.0, self.target_entropy, self.alpha if tune else None,
-                       ws, self.actor_grad, self.actor_stats)
+                       ws, self.actor_grad, self.actor_stats, layers=self.layers)
         self.actor_opt.step_(self.actor, self.actor_grad, self.max_grad_norm)
         from .ops import polyak_
 
